@@ -11,6 +11,19 @@ synthetic Reddit-sized graph (V=232,965, E=114,615,891, symmetric power-law with
 self loops), hidden D=256, k=16 -- BASELINE.json configs[1] at k=16.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--graph reddit] [--k 16]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs: it builds the graph and the plans, warms up,
+times the K steps, writes the outputs with --dump-outputs, and prints the result line.  --full
+adds what takes work of its own: the adjoint sanity check on the timed buffers, at N > 1 the
+check of every rank's rows against the unsharded result, the pull locality of the graph, the
+top-k encode time, the rocSPARSE SpMM denominators and the CPU baselines (the --no-* options
+drop single ones of these); their keys are absent from a plain run's line.
+
+--dump-outputs DIR writes what the last timed step left in the buffers its caller receives, as
+float32 DIR/y.npy (forward output rows) and DIR/gs.npy (the CBSR-shaped gradient rows); an array
+over DUMP_BYTES_EACH is cut to a fixed sample of its rows (dump_rows).  The inputs depend only
+on the arguments, so two builds can be compared output for output.
 
 N > 1, one rank per GPU: vertex-range shards balanced by nnz; per step an RCCL
 all-gather of the CBSR rows before the forward and a reduce-scatter of the
@@ -135,6 +148,32 @@ def binding_roofline(t_ms, compulsory, rec):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES_EACH = 24 << 20  # two arrays per dump: well inside 64 MB in all
+
+
+def dump_rows(n_rows, row_bytes):
+    """Row indices (sorted, int64) of an [n_rows, ...] output that --dump-outputs keeps: every
+    row when the array fits DUMP_BYTES_EACH, else a sample of that size drawn without
+    replacement by a generator seeded with the array's shape alone, so that it is the same
+    from run to run and from build to build."""
+    keep = max(1, DUMP_BYTES_EACH // max(1, row_bytes))
+    if n_rows <= keep:
+        return np.arange(n_rows, dtype=np.int64)
+    rng = np.random.default_rng([n_rows, row_bytes])
+    return np.sort(rng.choice(n_rows, keep, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, arrays):
+    """Write each (name, tensor) as float32 path/<name>.npy, rows cut by dump_rows."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        rows = dump_rows(t.shape[0], t[0].numel() * 4 if t.shape[0] else 4)
+        if rows.size < t.shape[0]:
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"),
+                np.ascontiguousarray(t.detach().float().cpu().numpy()))
 
 
 def alg_bytes(V, E, D, k, Vc=None):
@@ -408,6 +447,13 @@ def main():
     ap.add_argument("--dim", type=int, default=None)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--chunk", type=int, default=0, help="tokens per work item (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the adjoint and "
+                         "unsharded self-checks, pull locality, top-k time, rocSPARSE and CPU "
+                         "baselines (see the module docstring)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs as float32 "
+                         "DIR/y.npy and DIR/gs.npy (rank 0's rows at N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rocsparse", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -652,20 +698,28 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- sanity: forward/backward adjoint identity on the timed buffers (summed over ranks:
-    # each rank's output rows against its G rows, its CBSR rows against their gradient)
-    a = (y.double() * l_G.double()).sum()
     gs_own = gs_all[:nl] if world == 1 else gs_loc[:nl]
-    b = (cv_loc[:nl].double() * gs_own.double()).sum()
-    if dist:
-        ab = torch.stack([a, b])
-        if backend != "nccl":
-            ab = ab.cpu()
-        dist.all_reduce(ab)
-        a, b = ab[0], ab[1]
-    adj_err = abs(float(a) - float(b)) / max(1.0, abs(float(a)))
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left: the forward's output rows and the CBSR-shaped gradient
+        # of this rank's rows (N > 1: rank 0's shard)
+        dump_outputs(args.dump_outputs, [("y", y), ("gs", gs_own)])
+        stage(f"outputs written to {args.dump_outputs}")
 
-    if world > 1:
+    adj_err = None
+    if args.full:
+        # ---- sanity: forward/backward adjoint identity on the timed buffers (summed over
+        # ranks: each rank's output rows against its G rows, its CBSR rows against their gradient)
+        a = (y.double() * l_G.double()).sum()
+        b = (cv_loc[:nl].double() * gs_own.double()).sum()
+        if dist:
+            ab = torch.stack([a, b])
+            if backend != "nccl":
+                ab = ab.cpu()
+            dist.all_reduce(ab)
+            a, b = ab[0], ab[1]
+        adj_err = abs(float(a) - float(b)) / max(1.0, abs(float(a)))
+
+    if world > 1 and args.full:
         # every rank holds the whole graph and X/G (same seeds): recompute its rows unsharded.
         # Ranks sharing a device (the gloo rehearsal) take turns: eight concurrent unsharded
         # products-sized backwards (a 15.8 GB contribution array each) could exhaust the one
@@ -719,7 +773,7 @@ def main():
         "bwd_ms_mean": round(float(np.mean(bwd_ms)), 4),
         "fwd_gteps": round(El / fwd_avg / 1e6, 3), "bwd_gteps": round(El / bwd_avg / 1e6, 3),
         "fwd_alg_GBs": round(B_f / fwd_avg / 1e6, 1), "bwd_alg_GBs": round(B_b / bwd_avg / 1e6, 1),
-        "adjoint_rel_err": adj_err, "max_deg": int(deg.max()), "chunk": args.chunk,
+        "max_deg": int(deg.max()), "chunk": args.chunk,
         "bwd_mode": args.bwd_mode, "backward_plan_s": round(t_plan, 4),
         "build_config": build_cfg,
         "edge_sel_stream": es is not None or (pipelined and any(
@@ -729,9 +783,11 @@ def main():
     }
     if args.reorder:
         extra["reorder_s"] = None if t_reorder is None else round(t_reorder, 3)
-    # edges per occupied (source row, pull bucket): the locality the pull backward feeds on
-    extra["pull_locality"] = round(
-        mk.pull_locality(l_row_ptr, l_col, int(mk._lib().maxk_pull_shift(k))), 3)
+    if args.full:
+        extra["adjoint_rel_err"] = adj_err
+        # edges per occupied (source row, pull bucket): the locality the pull backward feeds on
+        extra["pull_locality"] = round(
+            mk.pull_locality(l_row_ptr, l_col, int(mk._lib().maxk_pull_shift(k))), 3)
     if args.bwd_mode == "hybrid":  # share of the edges the pulled tiles hold, and their count
         extra["hybrid_pull_edges_frac"] = round(plan[4].shape[0] / max(1, El), 4)
         extra["hybrid_pull_tiles"] = int(plan[0].numel())
@@ -743,8 +799,10 @@ def main():
         extra["fwd_l2_miss_GB"] = round(f_traffic / 1e9, 3)
         extra["fwd_l2_miss_GBs"] = round(f_traffic / (fwd_avg * 1e-3) / 1e9, 1)
     if world > 1:
-        extra.update({"dist_check_fwd_max_rel_err": dist_err[0],
-                      "dist_check_bwd_max_rel_err": dist_err[1], "dist_backend": backend,
+        if args.full:
+            extra.update({"dist_check_fwd_max_rel_err": dist_err[0],
+                          "dist_check_bwd_max_rel_err": dist_err[1]})
+        extra.update({"dist_backend": backend,
                       "dist_mode": shard.mode, "dist_pipeline": shard.pipeline,
                       # the pipelined gather exchanged transport records (maxk_dist._records)
                       "dist_records": bool(pipelined and shard._records(k, D)),
@@ -756,7 +814,7 @@ def main():
                       "edges_this_rank0": El, "cols_this_rank0": n_cols,
                       "exchange_bytes_rank0": shard.exchange_bytes(k)})
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # CBSR encode (top-k) and the dense rocSPARSE SpMM denominator, outside the timed region
         for _ in range(3):
             mk.topk_cbsr(X, k)
@@ -799,7 +857,7 @@ def main():
             del dense, y_lib
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(row_ptr, col, val, cv_all, ci_all, G, D, args.cpu_seconds, deg=deg)
         if not args.no_cpu_spmm:
             extra.update(cpu_spmm_baselines(row_ptr, col, val, mk.cbsr_scatter_dense(cv_all, ci_all, D)))

@@ -368,3 +368,27 @@ def test_bench_binding_roofline_and_traffic_order():
     b = bench.binding_roofline(1.0, 1e9, None)
     assert b["bound"] == "hbm_compulsory" and b["frac"] == 0.125
 
+
+
+def test_bench_dump_rows_and_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an array within DUMP_BYTES_EACH is written whole, a larger one
+    as the same sorted sample of rows every time; files are float32 .npy."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert 2 * bench.DUMP_BYTES_EACH <= 64e6  # two arrays per dump
+    assert np.array_equal(bench.dump_rows(1000, 1024), np.arange(1000))
+    n, row_bytes = 232965, 1024  # the default workload's forward output
+    rows = bench.dump_rows(n, row_bytes)
+    assert rows.size == bench.DUMP_BYTES_EACH // row_bytes < n
+    assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < n
+    assert np.array_equal(rows, bench.dump_rows(n, row_bytes))
+    t = torch.arange(12, dtype=torch.float64).reshape(4, 3)
+    bench.dump_outputs(str(tmp_path / "whole"), [("a", t)])
+    a = np.load(tmp_path / "whole" / "a.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, t.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES_EACH", 24)  # room for two of the four 12-byte rows
+    bench.dump_outputs(str(tmp_path / "cut"), [("a", t)])
+    a = np.load(tmp_path / "cut" / "a.npy")
+    assert a.shape == (2, 3) and np.array_equal(a, t.numpy()[bench.dump_rows(4, 12)])

@@ -164,7 +164,8 @@ def test_bench_self_launch(graph, k, gpus, records):
     env.pop("MAXK_VALIDATE", None)  # the bench validates its graph once itself
     root = os.path.dirname(HERE)
     p = subprocess.run([sys.executable, "-u", os.path.join(root, "bench.py"), "--gpus", str(gpus),
-                        "--graph", graph, "--k", str(k), "--steps", "2", "--warmup", "1"],
+                        "--graph", graph, "--k", str(k), "--steps", "2", "--warmup", "1",
+                        "--full"],  # --full: the unsharded self-check and the adjoint identity
                        env=env, cwd=root, capture_output=True, text=True, timeout=280)
     if p.returncode != 0:
         # a failing rank's own traceback sits above torch.distributed.run's summary

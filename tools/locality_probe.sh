@@ -3,7 +3,7 @@
 # and after maxk_graph.locality_order: bench lines per backward mode, halo bytes at N = 2/4/8.
 set -eo pipefail
 O=gpurun_out/locality; mkdir -p $O
-run() { local name=$1; shift; timeout -k 10 300 python bench.py --graph products_comm --no-cpu-baseline --no-cpu-spmm "$@" > $O/$name.json 2> $O/$name.err; echo "$name $(python -c "import json; d=json.load(open('$O/$name.json')); e=d['extra']; print(d['value'], e['fwd_ms'], e['bwd_ms'], e['bwd_mode'], d['roofline']['frac'], e.get('pull_locality'), e.get('reorder_s'), e.get('rocsparse_spmm_ms'))")"; }
+run() { local name=$1; shift; timeout -k 10 300 python bench.py --full --graph products_comm --no-cpu-baseline --no-cpu-spmm "$@" > $O/$name.json 2> $O/$name.err; echo "$name $(python -c "import json; d=json.load(open('$O/$name.json')); e=d['extra']; print(d['value'], e['fwd_ms'], e['bwd_ms'], e['bwd_mode'], d['roofline']['frac'], e.get('pull_locality'), e.get('reorder_s'), e.get('rocsparse_spmm_ms'))")"; }
 run random
 run random_pull --bwd-mode pull --no-rocsparse
 run ordered --reorder

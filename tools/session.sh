@@ -8,7 +8,7 @@
 # here.  Steps:
 #   tests     pytest -m gpu (the whole GPU suite)
 #   smoke     __graft_entry__.smoke()
-#   bench     the default bench line (BENCH contract), with CPU baselines
+#   bench     the default bench line (BENCH contract) with --full: checks, library and CPU baselines
 #   stats     rocprofv3 --kernel-trace --stats of a short default bench
 #   pmc       FETCH_SIZE and WRITE_SIZE of the same short bench, one rocprofv3 --pmc pass each
 #   presets   every preset with its denominators (rocSPARSE every algorithm; CPU baselines
@@ -77,7 +77,7 @@ step_smoke() {
 }
 step_bench() {
   mkdir -p $O
-  timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err
+  timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err
   cut -c1-400 $O/bench.json
 }
 step_stats() {
@@ -100,7 +100,8 @@ preset() {  # preset <name> <bench args...>
   local name=$1; shift
   local cpu="--no-cpu-baseline --no-cpu-spmm"
   [ "${PRESET_CPU:-0}" = 1 ] && cpu="--cpu-seconds 6"
-  timeout -k 10 400 python bench.py $cpu "$@" > $O/presets/$name.json 2> $O/presets/$name.err
+  timeout -k 10 400 python bench.py --full $cpu "$@" > $O/presets/$name.json \
+    2> $O/presets/$name.err
   python - "$O/presets/$name.json" "$name" <<'EOF'
 import json, sys
 d = json.load(open(sys.argv[1])); e = d["extra"]
@@ -305,7 +306,7 @@ rehearse_one() {  # rehearse_one <name> <ranks> <bench args...>
   local n=$1 w=$2; shift 2
   MAXK_DIST_BACKEND=gloo timeout -k 10 420 python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node $w --master-addr 127.0.0.1 --master-port $((29500 + w)) bench.py \
-    --gpus $w --steps 5 --warmup 2 "$@" > $O/rehearsal/$n.json 2> $O/rehearsal/$n.err
+    --gpus $w --steps 5 --warmup 2 --full "$@" > $O/rehearsal/$n.json 2> $O/rehearsal/$n.err
   python - $O/rehearsal/$n.json $n <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); e = d["extra"]
