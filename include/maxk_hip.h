@@ -18,6 +18,19 @@
  *   dense   f32 [rows, dim_origin]
  *   warp4   int32 [W, 4] = (row, loc, len, 0)
  * Limits: 1 <= k <= dim_origin <= 256 (the selector is uint8).
+ *
+ * Numerics (tests/numerics.py, tests/test_numerics_gpu.py): every element of the forward and
+ * of the backward matches exact arithmetic to within (n + 8) * 2^-24 * sum|terms|, n its number
+ * of addends (edges times repeated selectors, plus one for an accumulate prefill) -- at any
+ * magnitude, fp32 subnormals included, not only near 1; an element without addends is exactly
+ * 0.  Inf and NaN in cbsr_val and grad_out propagate as the IEEE sum of the selected terms:
+ * terms behind skipped, repeated or out-of-range selectors follow the same rule as finite
+ * values (a NaN behind a selector >= dim_origin or in a vertex no edge reads reaches nothing),
+ * and any NaN bit pattern is handled, the transport records' own skip marker included.
+ * Non-finite edge weights or row_div are outside the contract (the dense route multiplies
+ * unselected zeros by the weight).  The forward (every form) and the csc and dense backwards
+ * sum in a fixed order: bitwise repeatable, and bitwise equivariant under a power-of-two scale
+ * of the values away from overflow and underflow.
  */
 #ifndef MAXK_HIP_H_
 #define MAXK_HIP_H_
@@ -135,6 +148,9 @@ int maxk_spgemm_forward_records(const int32_t *row_ptr, const int32_t *col_idx,
  * Replaces: spmm_kernel_opt2_sparse_backward_v3 (kernels/spmm_maxk_backward.cu:15-115),
  *           spmm_kernel_opt2_sparse_backward_v3_wrapper (cuda_kernel_wrappers.cu:58-76)
  *           and the /out_degrees of maxk_spgemm_function.py:154-155.
+ * This entry point (the "atomic" mode) adds with fp32 global atomics, built with
+ * -munsafe-fp-atomics: measured on gfx950, they keep fp32 subnormals (gradients at 2^-130 meet
+ * the bound of the top comment with its 2^-149 floor; nothing resolvable is flushed to 0).
  * ------------------------------------------------------------------------- */
 size_t maxk_sspmm_backward_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
                                           int32_t dim_origin, int32_t dim_k, int32_t chunk_edges);
