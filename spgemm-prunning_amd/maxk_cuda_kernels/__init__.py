@@ -24,14 +24,14 @@ import contextlib
 import ctypes
 import os
 import warnings
-import weakref
 from typing import List, Optional, Tuple
 
 import torch
 
 from . import _capi
+from ._cache import TensorCache
 
-_capi.load()  # ImportError here <=> extension missing (callers test this, like the reference)
+_L = _capi.load()  # ImportError here <=> extension missing (callers test this, like the reference)
 
 __all__ = [
     "spmm_maxk_forward", "spmm_maxk_backward", "cuda_topk_maxk", "cuda_topk_maxk_float",
@@ -47,13 +47,14 @@ __all__ = [
     "build_warp4_metadata", "warp4_to_indptr",
     "spgemm_forward", "sspmm_backward", "DenseSpMMPlan", "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
+    "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
 ]
 
 FULL_DIM = 256  # the reference binding's fixed output width (cuda_kernel_bindings.cpp:70)
 
 
 def _lib():
-    return _capi.load()
+    return _L
 
 
 def version() -> int:
@@ -75,14 +76,7 @@ def _validate_default() -> bool:
     return _validate_mode() == "always"
 
 
-_CHECKED: "dict" = {}
-
-
-def _ver(t):
-    """Version counter of a cached-on tensor.  Inference tensors have none (reading it raises):
-    they get a fresh token, so a cache entry on one never hits and the plan or check is redone
-    per call, which is always correct."""
-    return object() if t.is_inference() else t._version
+_CHECKED = TensorCache()
 
 
 def _check_graph_once(row_ptr, col_idx, num_cols):
@@ -92,21 +86,15 @@ def _check_graph_once(row_ptr, col_idx, num_cols):
     a selector >= D contributes nothing in every kernel (the forward sends it to a trash
     column, the two-phase and atomic backwards read a zeroed LDS slot, the pull backward
     gathers 0 for it), so it cannot read outside G or another row of it."""
-    key = (id(row_ptr), id(col_idx))
-    hit = _CHECKED.get(key)
-    if hit is not None:
-        rr, cr, rv, cv, nc = hit
-        if rr() is row_ptr and cr() is col_idx and rv == _ver(row_ptr) and \
-                cv == _ver(col_idx) and nc == num_cols:
-            return
-    _validate_graph(row_ptr, col_idx, num_cols, col_idx.numel())
-    if key not in _CHECKED:
-        weakref.finalize(col_idx, _CHECKED.pop, key, None)
-    _CHECKED[key] = (weakref.ref(row_ptr), weakref.ref(col_idx), _ver(row_ptr),
-                     _ver(col_idx), int(num_cols))
+    def build():
+        _validate_graph(row_ptr, col_idx, num_cols, col_idx.numel())
+        return True  # the entry says: checked
+    _CHECKED.get((row_ptr, col_idx), (int(num_cols),), build)
 
 
 def _validate_call(validate, row_ptr, col_idx, num_cols, sel, D):
+    if validate is False:
+        return  # no check asked for: no need to ask whether one could run
     if torch.cuda.is_current_stream_capturing():
         return  # a range check synchronises the host: impossible inside a hipGraph capture
     if validate if validate is not None else _validate_default():
@@ -145,9 +133,37 @@ _NO_SWITCH = contextlib.nullcontext()
 
 def _on(dev):
     """torch.cuda.device(dev), or nothing when dev is already the current device (the
-    context manager costs ~2.6 us per call)."""
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    return _NO_SWITCH if idx == torch.cuda.current_device() else torch.cuda.device(dev)
+    context manager costs ~2.6 us per call).  `dev` holds a tensor, so HIP is initialised and
+    the raw accessor serves, as in _stream."""
+    cur = torch._C._cuda_getDevice()
+    return _NO_SWITCH if dev.index is None or dev.index == cur else torch.cuda.device(dev)
+
+
+def _launch(dev, name, *args):
+    """The C-ABI call `name`(*args) with `dev` current; raises on a non-zero status."""
+    with _on(dev):
+        _capi.check(getattr(_L, name)(*args), name)
+
+
+def _sized(dev, name, *args) -> int:
+    """A size the library derives from the *current* device (its CU count): asked with `dev`
+    current, like the launch it sizes."""
+    with _on(dev):
+        return int(getattr(_L, name)(*args))
+
+
+def _workspace(dev, size_name, *size_args) -> torch.Tensor:
+    """uint8 scratch on `dev` of `size_name`(*size_args) bytes (never empty)."""
+    return torch.empty(max(_sized(dev, size_name, *size_args), 1), dtype=torch.uint8, device=dev)
+
+
+def _launch_ws(dev, name, size_name, size_args, args, tail=()):
+    """_workspace and _launch under one device switch, for a call that runs straight after its
+    size query: `name`(*args, workspace, its bytes, torch's current stream on dev, *tail)."""
+    with _on(dev):
+        n = max(getattr(_L, size_name)(*size_args), 1)
+        ws = torch.empty(n, dtype=torch.uint8, device=dev)
+        _capi.check(getattr(_L, name)(*args, ws.data_ptr(), n, _stream(dev), *tail), name)
 
 
 def _validate_graph(row_ptr, col_idx, num_cols, num_e):
@@ -174,10 +190,8 @@ def warp4_to_indptr(warp4_metadata: torch.Tensor, num_v: int,
     W = warp4_metadata.numel() // 4 if num_warps is None else min(int(num_warps),
                                                                    warp4_metadata.numel() // 4)
     row_ptr = torch.empty(num_v + 1, dtype=torch.int32, device=warp4_metadata.device)
-    with torch.cuda.device(warp4_metadata.device):
-        _capi.check(_lib().maxk_warp4_to_row_ptr(_ptr(warp4_metadata), W, num_v, _ptr(row_ptr),
-                                                 _stream(warp4_metadata.device)),
-                    "maxk_warp4_to_row_ptr")
+    _launch(warp4_metadata.device, "maxk_warp4_to_row_ptr", _ptr(warp4_metadata), W, num_v,
+            _ptr(row_ptr), _stream(warp4_metadata.device))
     return row_ptr
 
 
@@ -187,16 +201,11 @@ def build_warp4_metadata(indptr: torch.Tensor, warp_max_nz: int = 64) -> torch.T
     _need(indptr, "indptr", torch.int32)
     dev = indptr.device
     V = indptr.numel() - 1
-    with _on(dev):
-        s = _stream(dev)
-        n = ctypes.c_int64(0)
-        _capi.check(_lib().maxk_warp4_count(_ptr(indptr), V, warp_max_nz, ctypes.byref(n), s),
-                    "maxk_warp4_count")
-        out = torch.empty(4 * n.value, dtype=torch.int32, device=dev)
-        ws = torch.empty(max(1, _lib().maxk_warp4_build_workspace_size(V)), dtype=torch.uint8,
-                         device=dev)
-        _capi.check(_lib().maxk_warp4_build(_ptr(indptr), V, warp_max_nz, _ptr(out), n.value,
-                                            _ptr(ws), ws.numel(), s), "maxk_warp4_build")
+    n = ctypes.c_int64(0)
+    _launch(dev, "maxk_warp4_count", _ptr(indptr), V, warp_max_nz, ctypes.byref(n), _stream(dev))
+    out = torch.empty(4 * n.value, dtype=torch.int32, device=dev)
+    _launch_ws(dev, "maxk_warp4_build", "maxk_warp4_build_workspace_size", (V,),
+               (_ptr(indptr), V, warp_max_nz, _ptr(out), n.value))
     return out
 
 
@@ -223,6 +232,30 @@ def load_warp4_metadata_csc(graph_name: str, num_warps: int = 12,
 
 
 # --------------------------------------------------------------------------- hot path
+def _forward_common(indptr, indices, values, num_cols, k, sel, D, row_div, chunk, out, accumulate,
+                    validate, dev):
+    """What spgemm_forward and spgemm_forward_records share once their own operands passed: the
+    other input checks and `out`.  Returns (out, (num_rows, num_cols, E, D, k, chunk)), the
+    shape arguments of both the kernel and its workspace size."""
+    if values.numel() != indices.numel():
+        raise RuntimeError("values and indices must have the same length")
+    num_rows = indptr.numel() - 1
+    if row_div is not None:
+        _need(row_div, "row_div", torch.float32)
+        if row_div.numel() != num_rows:
+            raise RuntimeError("row_div must have num_rows entries")
+    _validate_call(validate, indptr, indices, num_cols, sel, D)
+    if out is None:
+        if accumulate:
+            raise RuntimeError("accumulate=True needs out=")
+        out = torch.empty(num_rows, D, dtype=torch.float32, device=dev)
+    else:
+        _need(out, "out", torch.float32)
+        if tuple(out.shape) != (num_rows, D):
+            raise RuntimeError("out must be [num_rows, dim_origin]")
+    return out, (num_rows, num_cols, indices.numel(), D, k, chunk)
+
+
 def spgemm_forward(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
                    cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor, dim_origin: int,
                    row_div: Optional[torch.Tensor] = None, chunk: int = 0,
@@ -238,49 +271,21 @@ def spgemm_forward(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Te
                      (values, "values", torch.float32), (cbsr_val, "input_data", torch.float32),
                      (cbsr_idx, "sparse_selector", torch.uint8)):
         _need(t, n, dt)
-    num_rows = indptr.numel() - 1
     num_cols, k = (cbsr_val.shape[0], cbsr_val.shape[1]) if cbsr_val.dim() == 2 else (0, 0)
     if cbsr_idx.shape != cbsr_val.shape:
         raise RuntimeError("input_data and sparse_selector must have the same [V, k] shape")
-    if values.numel() != indices.numel():
-        raise RuntimeError("values and indices must have the same length")
-    D = int(dim_origin)
-    if row_div is not None:
-        _need(row_div, "row_div", torch.float32)
-        if row_div.numel() != num_rows:
-            raise RuntimeError("row_div must have num_rows entries")
-    _validate_call(validate, indptr, indices, num_cols, cbsr_idx, D)
-    dev = cbsr_val.device
-    if out is None:
-        if accumulate:
-            raise RuntimeError("accumulate=True needs out=")
-        out = torch.empty(num_rows, D, dtype=torch.float32, device=dev)
-    else:
-        _need(out, "out", torch.float32)
-        if tuple(out.shape) != (num_rows, D):
-            raise RuntimeError("out must be [num_rows, dim_origin]")
-    L = _lib()
-    E = indices.numel()
-    ws_bytes = L.maxk_spgemm_forward_workspace_size(num_rows, num_cols, E, D, k, chunk)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    out, shape = _forward_common(indptr, indices, values, num_cols, k, cbsr_idx, int(dim_origin),
+                                 row_div, chunk, out, accumulate, validate, cbsr_val.device)
+    tail = ()
     if edge_sel_out is not None:
         _need(edge_sel_out, "edge_sel_out", torch.uint8)
-        if tuple(edge_sel_out.shape) != (E, k):
+        if tuple(edge_sel_out.shape) != (shape[2], k):
             raise RuntimeError("edge_sel_out must be [num_e, k]")
-        fn = L.maxk_spgemm_forward_accumulate_sel if accumulate else L.maxk_spgemm_forward_sel
-        with _on(dev):
-            _capi.check(fn(
-                _ptr(indptr), _ptr(indices), _ptr(values), _ptr(cbsr_val), _ptr(cbsr_idx),
-                _ptr(row_div), _ptr(out), num_rows, num_cols, E, D, k, chunk, _ptr(ws),
-                ws.numel(), _stream(dev), _ptr(edge_sel_out)),
-                "maxk_spgemm_forward_accumulate_sel" if accumulate else "maxk_spgemm_forward_sel")
-        return out
-    fn = L.maxk_spgemm_forward_accumulate if accumulate else L.maxk_spgemm_forward
-    with _on(dev):
-        _capi.check(fn(
-            _ptr(indptr), _ptr(indices), _ptr(values), _ptr(cbsr_val), _ptr(cbsr_idx),
-            _ptr(row_div), _ptr(out), num_rows, num_cols, E, D, k, chunk, _ptr(ws), ws.numel(),
-            _stream(dev)), "maxk_spgemm_forward_accumulate" if accumulate else "maxk_spgemm_forward")
+        tail = (_ptr(edge_sel_out),)
+    _launch_ws(cbsr_val.device, "maxk_spgemm_forward" + ("_accumulate" if accumulate else "")
+               + ("_sel" if tail else ""), "maxk_spgemm_forward_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(cbsr_val), _ptr(cbsr_idx),
+                _ptr(row_div), _ptr(out), *shape), tail)
     return out
 
 
@@ -303,10 +308,8 @@ def cbsr_records(cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor, dim_origin: int
         out = torch.empty(V, 5 * k, dtype=torch.uint8, device=cbsr_val.device)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (V, 5 * k) or not out.is_contiguous():
         raise RuntimeError("out must be a contiguous uint8 [V, 5k] tensor")
-    with _on(cbsr_val.device):
-        _capi.check(_lib().maxk_cbsr_records(_ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), V,
-                                             int(dim_origin), k, _stream(cbsr_val.device)),
-                    "maxk_cbsr_records")
+    _launch(cbsr_val.device, "maxk_cbsr_records", _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), V,
+            int(dim_origin), k, _stream(cbsr_val.device))
     return out
 
 
@@ -327,37 +330,18 @@ def spgemm_forward_records(indptr: torch.Tensor, indices: torch.Tensor, values: 
     k = int(k)
     if k <= 0 or rec.dim() != 2 or rec.shape[1] != 5 * k:
         raise RuntimeError("rec must be [num_cols, 5k]")
-    if values.numel() != indices.numel():
-        raise RuntimeError("values and indices must have the same length")
-    num_rows, num_cols, E, D = indptr.numel() - 1, rec.shape[0], indices.numel(), int(dim_origin)
-    dev = rec.device
-    if row_div is not None:
-        _need(row_div, "row_div", torch.float32)
-        if row_div.numel() != num_rows:
-            raise RuntimeError("row_div must have num_rows entries")
     # the selectors are the records' last k bytes: a strided view, read only by the selector
     # range check (validate=True); the graph check is what bounds the kernel's record reads
-    _validate_call(validate, indptr, indices, num_cols, rec[:, 4 * k:], D)
-    if out is None:
-        if accumulate:
-            raise RuntimeError("accumulate=True needs out=")
-        out = torch.empty(num_rows, D, dtype=torch.float32, device=dev)
-    else:
-        _need(out, "out", torch.float32)
-        if tuple(out.shape) != (num_rows, D):
-            raise RuntimeError("out must be [num_rows, dim_origin]")
-    L = _lib()
-    ws_bytes = L.maxk_spgemm_forward_workspace_size(num_rows, num_cols, E, D, k, chunk)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    with _on(dev):
-        _capi.check(L.maxk_spgemm_forward_records(
-            _ptr(indptr), _ptr(indices), _ptr(values), _ptr(rec), _ptr(row_div), _ptr(out),
-            num_rows, num_cols, E, D, k, chunk, _ptr(ws), ws.numel(), _stream(dev),
-            1 if accumulate else 0), "maxk_spgemm_forward_records")
+    out, shape = _forward_common(indptr, indices, values, rec.shape[0], k, rec[:, 4 * k:],
+                                 int(dim_origin), row_div, chunk, out, accumulate, validate,
+                                 rec.device)
+    _launch_ws(rec.device, "maxk_spgemm_forward_records", "maxk_spgemm_forward_workspace_size",
+               shape, (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(rec), _ptr(row_div),
+                       _ptr(out), *shape), (1 if accumulate else 0,))
     return out
 
 
-_PLAN_CACHE: "dict" = {}
+_PLAN_CACHE = TensorCache()
 
 
 def transpose_plan(indices: torch.Tensor, num_cols: int, cache: bool = True):
@@ -365,32 +349,19 @@ def transpose_plan(indices: torch.Tensor, num_cols: int, cache: bool = True):
     pointer and, per CSC slot, the CSR edge id it holds.  Built once per graph on the GPU
     (stable radix sort); cached per `indices` tensor object (and its version counter)."""
     _need(indices, "indices", torch.int32)
-    key = id(indices)
-    hit = _PLAN_CACHE.get(key)
-    if cache and hit is not None:
-        ref, nc, ver, plan = hit
-        if ref() is indices and nc == num_cols and ver == _ver(indices):
-            return plan
-    dev = indices.device
-    E = indices.numel()
-    col_ptr = torch.empty(num_cols + 1, dtype=torch.int32, device=dev)
-    csc_eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-    L = _lib()
-    ws = torch.empty(max(1, L.maxk_transpose_plan_workspace_size(num_cols, E)), dtype=torch.uint8,
-                     device=dev)
-    with _on(dev):
-        _capi.check(L.maxk_transpose_plan(_ptr(indices), num_cols, E, _ptr(col_ptr),
-                                          _ptr(csc_eid), _ptr(ws), ws.numel(), _stream(dev)),
-                    "maxk_transpose_plan")
-    plan = (col_ptr, csc_eid)
-    if cache:
-        if key not in _PLAN_CACHE:
-            weakref.finalize(indices, _PLAN_CACHE.pop, key, None)
-        _PLAN_CACHE[key] = (weakref.ref(indices), int(num_cols), _ver(indices), plan)
-    return plan
+
+    def build():
+        dev = indices.device
+        E = indices.numel()
+        col_ptr = torch.empty(num_cols + 1, dtype=torch.int32, device=dev)
+        csc_eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
+        _launch_ws(dev, "maxk_transpose_plan", "maxk_transpose_plan_workspace_size",
+                   (num_cols, E), (_ptr(indices), num_cols, E, _ptr(col_ptr), _ptr(csc_eid)))
+        return col_ptr, csc_eid
+    return _PLAN_CACHE.get((indices,), (int(num_cols),), build, cache)
 
 
-_DENSE_CACHE: "dict" = {}
+_DENSE_CACHE = TensorCache()
 
 
 def dense_plan(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor, num_cols: int,
@@ -402,33 +373,20 @@ def dense_plan(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor
     for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
                      (values, "values", torch.float32)):
         _need(t, n, dt)
-    key = (id(indptr), id(indices), id(values))
-    hit = _DENSE_CACHE.get(key)
-    if cache and hit is not None:
-        rp, ri, rv, nc, pv, vi, vv, plan = hit
-        if (rp() is indptr and ri() is indices and rv() is values and nc == num_cols
-                and pv == _ver(indptr) and vi == _ver(indices) and vv == _ver(values)):
-            return plan
-    col_ptr, csc_eid = transpose_plan(indices, num_cols, cache=False)
-    dev = indices.device
-    E = indices.numel()
-    t_src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-    t_w = torch.empty(max(E, 1), dtype=torch.float32, device=dev)[:E]
-    with _on(dev):
-        _capi.check(_lib().maxk_dense_plan(_ptr(indptr), _ptr(values), _ptr(csc_eid),
-                                           indptr.numel() - 1, E, _ptr(t_src), _ptr(t_w),
-                                           _stream(dev)), "maxk_dense_plan")
-    plan = (col_ptr, t_src, t_w)
-    if cache:
-        if key not in _DENSE_CACHE:
-            for t in (indptr, indices, values):
-                weakref.finalize(t, _DENSE_CACHE.pop, key, None)
-        _DENSE_CACHE[key] = (weakref.ref(indptr), weakref.ref(indices), weakref.ref(values),
-                             int(num_cols), _ver(indptr), _ver(indices), _ver(values), plan)
-    return plan
+
+    def build():
+        col_ptr, csc_eid = transpose_plan(indices, num_cols, cache=False)
+        dev = indices.device
+        E = indices.numel()
+        t_src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
+        t_w = torch.empty(max(E, 1), dtype=torch.float32, device=dev)[:E]
+        _launch(dev, "maxk_dense_plan", _ptr(indptr), _ptr(values), _ptr(csc_eid),
+                indptr.numel() - 1, E, _ptr(t_src), _ptr(t_w), _stream(dev))
+        return col_ptr, t_src, t_w
+    return _DENSE_CACHE.get((indptr, indices, values), (int(num_cols),), build, cache)
 
 
-_BSORT_CACHE: "dict" = {}
+_BSORT_CACHE = TensorCache()
 
 
 def bsort_plan(indptr: torch.Tensor, indices: torch.Tensor, num_cols: int, k: int,
@@ -445,40 +403,24 @@ def bsort_plan(indptr: torch.Tensor, indices: torch.Tensor, num_cols: int, k: in
     if int(L.maxk_bsort_window(int(k))) <= 0:
         raise RuntimeError(f"bsort_plan: k must be a multiple of 4 in [4, 256], got {k}")
     shift = int(L.maxk_bucket_shift(int(k)))
-    key = (id(indptr), id(indices), int(k))
-    hit = _BSORT_CACHE.get(key)
-    if cache and hit is not None:
-        rp, ri, nc, pv, vi, plan = hit
-        if (rp() is indptr and ri() is indices and nc == num_cols and pv == _ver(indptr)
-                and vi == _ver(indices)):
-            return plan
-    dev = indices.device
-    E = indices.numel()
-    num_rows = indptr.numel() - 1
-    nb = int(L.maxk_bucket_count(num_cols, shift))
-    bptr = torch.empty(nb + 1, dtype=torch.int32, device=dev)
-    bpos = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-    bdst = torch.empty(max(E, 1), dtype=torch.uint16, device=dev)[:E]
-    wsrc = torch.empty(max(E, 1), dtype=torch.uint16, device=dev)[:E]
-    wrow = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-    ws = torch.empty(max(1, L.maxk_bsort_plan_workspace_size(num_cols, E)), dtype=torch.uint8,
-                     device=dev)
-    with _on(dev):
-        _capi.check(L.maxk_bsort_plan(_ptr(indptr), _ptr(indices), num_rows, num_cols, E, int(k),
-                                      shift, _ptr(bptr), _ptr(bpos), _ptr(bdst), _ptr(wsrc),
-                                      _ptr(wrow), _ptr(ws), ws.numel(), _stream(dev)),
-                    "maxk_bsort_plan")
-    plan = (bptr, bpos, bdst, wsrc, wrow, shift)
-    if cache:
-        if key not in _BSORT_CACHE:
-            for t in (indptr, indices):
-                weakref.finalize(t, _BSORT_CACHE.pop, key, None)
-        _BSORT_CACHE[key] = (weakref.ref(indptr), weakref.ref(indices), int(num_cols),
-                             _ver(indptr), _ver(indices), plan)
-    return plan
+
+    def build():
+        dev = indices.device
+        E = indices.numel()
+        nb = int(L.maxk_bucket_count(num_cols, shift))
+        bptr = torch.empty(nb + 1, dtype=torch.int32, device=dev)
+        bpos = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
+        bdst = torch.empty(max(E, 1), dtype=torch.uint16, device=dev)[:E]
+        wsrc = torch.empty(max(E, 1), dtype=torch.uint16, device=dev)[:E]
+        wrow = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
+        _launch_ws(dev, "maxk_bsort_plan", "maxk_bsort_plan_workspace_size", (num_cols, E),
+                   (_ptr(indptr), _ptr(indices), indptr.numel() - 1, num_cols, E, int(k), shift,
+                    _ptr(bptr), _ptr(bpos), _ptr(bdst), _ptr(wsrc), _ptr(wrow)))
+        return bptr, bpos, bdst, wsrc, wrow, shift
+    return _BSORT_CACHE.get((indptr, indices), (int(k), int(num_cols)), build, cache)
 
 
-_PULL_CACHE: dict = {}
+_PULL_CACHE = TensorCache()
 
 
 def pull_plan(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor, num_cols: int,
@@ -502,47 +444,30 @@ def pull_plan(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
     shift = int(L.maxk_pull_shift(int(k))) if shift is None else int(shift)
     if shift < 0:
         raise RuntimeError(f"pull_plan: invalid k {k}")
-    if slices:
-        S = int(slices)
-    else:  # sized by the CU count of the device that holds the graph
-        with _on(indices.device):
-            S = int(L.maxk_pull_slices(num_rows, int(num_cols), int(dim), int(k)))
-    key = (id(indptr), id(indices), id(values), shift, S)
-    hit = _PULL_CACHE.get(key)
-    if cache and hit is not None:
-        rp, ri, rv, nc, pv, vi, vv, plan = hit
-        if (rp() is indptr and ri() is indices and rv() is values and nc == num_cols
-                and pv == _ver(indptr) and vi == _ver(indices)
-                and vv == _ver(values)):
-            return plan
-    dev = indices.device
-    E = indices.numel()
-    nb = int(L.maxk_bucket_count(num_cols, shift))
-    tptr = torch.empty(S * nb + 1, dtype=torch.int32, device=dev)
-    ent = torch.empty(max(E, 1), 2, dtype=torch.int32, device=dev)[:E]
-    ws = torch.empty(max(1, L.maxk_pull_plan_workspace_size(num_rows, num_cols, E, shift, S)),
-                     dtype=torch.uint8, device=dev)
-    with _on(dev):
-        _capi.check(L.maxk_pull_plan(_ptr(indptr), _ptr(indices), _ptr(values), num_rows,
-                                     num_cols, E, shift, S, _ptr(tptr), _ptr(ent), _ptr(ws),
-                                     ws.numel(), _stream(dev)), "maxk_pull_plan")
-    plan = (tptr, ent, shift, S)
-    if cache:
-        if key not in _PULL_CACHE:
-            for t in (indptr, indices, values):
-                weakref.finalize(t, _PULL_CACHE.pop, key, None)
-        _PULL_CACHE[key] = (weakref.ref(indptr), weakref.ref(indices), weakref.ref(values),
-                            int(num_cols), _ver(indptr), _ver(indices), _ver(values),
-                            plan)
-    return plan
+    # by default sized by the CU count of the device that holds the graph
+    S = int(slices) if slices else _sized(indices.device, "maxk_pull_slices", num_rows,
+                                          int(num_cols), int(dim), int(k))
+
+    def build():
+        dev = indices.device
+        E = indices.numel()
+        nb = int(L.maxk_bucket_count(num_cols, shift))
+        tptr = torch.empty(S * nb + 1, dtype=torch.int32, device=dev)
+        ent = torch.empty(max(E, 1), 2, dtype=torch.int32, device=dev)[:E]
+        _launch_ws(dev, "maxk_pull_plan", "maxk_pull_plan_workspace_size",
+                   (num_rows, num_cols, E, shift, S),
+                   (_ptr(indptr), _ptr(indices), _ptr(values), num_rows, num_cols, E, shift, S,
+                    _ptr(tptr), _ptr(ent)))
+        return tptr, ent, shift, S
+    return _PULL_CACHE.get((indptr, indices, values), (shift, S, int(num_cols)), build, cache)
 
 
-_HYBRID_CACHE: "dict" = {}
+_HYBRID_CACHE = TensorCache()
 MAXK_PULL_NO_REDUCE, MAXK_PULL_REDUCE_ONLY = 2, 4  # include/maxk_hip.h
 MAXK_HYBRID_PRESCALED = 1
 # maxk_backward_mode_auto's codes (include/maxk_hip.h MAXK_BWD_*)
 _MODE_OF_CODE = {0: "pull", 1: "csc", 3: "hybrid", 4: "atomic", 5: "bsort", 6: "dense"}
-_SIDE: "dict" = {}
+_SIDE: dict = {}
 
 
 def _side_stream(dev: torch.device) -> "torch.cuda.Stream":
@@ -573,56 +498,41 @@ def hybrid_plan(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tenso
         density = float(os.environ.get("MAXK_HYBRID_DENSITY", HYBRID_DENSITY))
     if k % 4:
         raise RuntimeError(f"hybrid backward needs k % 4 == 0, got k={k}")
-    key = (id(indptr), id(indices), id(values), int(k), int(dim), float(density))
-    hit = _HYBRID_CACHE.get(key)
-    if cache and hit is not None:
-        rp, ri, rv, nc, pv, vi, vv, plan = hit
-        if (rp() is indptr and ri() is indices and rv() is values and nc == num_cols
-                and pv == _ver(indptr) and vi == _ver(indices)
-                and vv == _ver(values)):
-            return plan
-    tptr, ent, shift, S = pull_plan(indptr, indices, values, num_cols, k, dim, cache=False)
-    dev = indices.device
-    L = _lib()
-    num_rows = indptr.numel() - 1
-    E = indices.numel()
-    nb = int(L.maxk_bucket_count(num_cols, shift))
-    nt = S * nb
-    i32 = dict(dtype=torch.int32, device=dev)
-    tile_list = torch.empty(max(nt, 1), **i32)
-    tile_ent = torch.empty(nt + 1, **i32)
-    bucket_ptr = torch.empty(nb + 1, **i32)
-    bucket_tiles = torch.empty(max(nt, 1), **i32)
-    ent_d = torch.empty(max(E, 1), 2, **i32)
-    off_ip = torch.empty(num_rows + 1, **i32)
-    off_ix = torch.empty(max(E, 1), **i32)
-    off_val = torch.empty(max(E, 1), dtype=torch.float32, device=dev)
-    ws = torch.empty(max(1, L.maxk_hybrid_plan_workspace_size(num_rows, num_cols, E, shift, S)),
-                     dtype=torch.uint8, device=dev)
-    counts = (ctypes.c_int64 * 3)()
-    with _on(dev):
-        _capi.check(L.maxk_hybrid_plan(
-            _ptr(indptr), _ptr(indices), _ptr(values), _ptr(tptr), _ptr(ent), num_rows, num_cols,
-            E, shift, S, float(density), _ptr(tile_list), _ptr(tile_ent), _ptr(bucket_ptr),
-            _ptr(bucket_tiles), _ptr(ent_d), _ptr(off_ip), _ptr(off_ix), _ptr(off_val), counts,
-            _ptr(ws), ws.numel(), _stream(dev)), "maxk_hybrid_plan")
-    n_t, n_p, n_o = (int(c) for c in counts)
-    del tptr, ent, ws
-    # the slices are views of their worst-case buffers; copies keep the plan compact
-    tile_list, bucket_tiles = tile_list[:n_t].clone(), bucket_tiles[:n_t].clone()
-    tile_ent = tile_ent[:n_t + 1].clone()
-    ent_d = ent_d[:n_p].clone()
-    off_ix, off_val = off_ix[:n_o].clone(), off_val[:n_o].clone()
-    off = (off_ip, off_ix, off_val, transpose_plan(off_ix, num_cols, cache=False))
-    plan = (tile_list, tile_ent, bucket_ptr, bucket_tiles, ent_d, shift, S, off)
-    if cache:
-        if key not in _HYBRID_CACHE:
-            for t in (indptr, indices, values):
-                weakref.finalize(t, _HYBRID_CACHE.pop, key, None)
-        _HYBRID_CACHE[key] = (weakref.ref(indptr), weakref.ref(indices), weakref.ref(values),
-                              int(num_cols), _ver(indptr), _ver(indices), _ver(values),
-                              plan)
-    return plan
+
+    def build():
+        tptr, ent, shift, S = pull_plan(indptr, indices, values, num_cols, k, dim, cache=False)
+        dev = indices.device
+        num_rows = indptr.numel() - 1
+        E = indices.numel()
+        nb = int(_lib().maxk_bucket_count(num_cols, shift))
+        nt = S * nb
+        i32 = dict(dtype=torch.int32, device=dev)
+        tile_list = torch.empty(max(nt, 1), **i32)
+        tile_ent = torch.empty(nt + 1, **i32)
+        bucket_ptr = torch.empty(nb + 1, **i32)
+        bucket_tiles = torch.empty(max(nt, 1), **i32)
+        ent_d = torch.empty(max(E, 1), 2, **i32)
+        off_ip = torch.empty(num_rows + 1, **i32)
+        off_ix = torch.empty(max(E, 1), **i32)
+        off_val = torch.empty(max(E, 1), dtype=torch.float32, device=dev)
+        counts = (ctypes.c_int64 * 3)()
+        _launch_ws(dev, "maxk_hybrid_plan", "maxk_hybrid_plan_workspace_size",
+                   (num_rows, num_cols, E, shift, S),
+                   (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(tptr), _ptr(ent), num_rows,
+                    num_cols, E, shift, S, float(density), _ptr(tile_list), _ptr(tile_ent),
+                    _ptr(bucket_ptr), _ptr(bucket_tiles), _ptr(ent_d), _ptr(off_ip), _ptr(off_ix),
+                    _ptr(off_val), counts))
+        n_t, n_p, n_o = (int(c) for c in counts)
+        del tptr, ent
+        # the slices are views of their worst-case buffers; copies keep the plan compact
+        tile_list, bucket_tiles = tile_list[:n_t].clone(), bucket_tiles[:n_t].clone()
+        tile_ent = tile_ent[:n_t + 1].clone()
+        ent_d = ent_d[:n_p].clone()
+        off_ix, off_val = off_ix[:n_o].clone(), off_val[:n_o].clone()
+        off = (off_ip, off_ix, off_val, transpose_plan(off_ix, num_cols, cache=False))
+        return tile_list, tile_ent, bucket_ptr, bucket_tiles, ent_d, shift, S, off
+    return _HYBRID_CACHE.get((indptr, indices, values),
+                             (int(k), int(dim), float(density), int(num_cols)), build, cache)
 
 
 BWD_MODES = ("auto", "pull", "csc", "atomic", "hybrid", "bsort", "dense")
@@ -630,10 +540,8 @@ BSORT_KMAX = 8  # MAXK_BSORT_KMAX: the auto rule's bsort limit
 _BSORT_WARNED: set = set()  # (id(indptr), k) already warned about
 
 
-_LOCALITY: "dict" = {}
-
-
-_SCALED: "dict" = {}
+_LOCALITY = TensorCache()
+_SCALED = TensorCache()
 
 
 def _scaled_entries(ent: torch.Tensor, tiles: Optional[torch.Tensor], tile_ent: torch.Tensor,
@@ -646,27 +554,21 @@ def _scaled_entries(ent: torch.Tensor, tiles: Optional[torch.Tensor], tile_ent: 
     Cached per entry tensor for one (row_div object, version): the degrees a layer divides by
     are the same tensor every call (maxk_layers.CSRGraph).  None when it would have to be built
     inside a stream capture."""
-    key = id(ent)
-    hit = _SCALED.get(key)
-    if hit is not None:
-        re, rd, ver, sc = hit
-        if re() is ent and rd() is row_div and ver == _ver(row_div):
-            return sc
+    sc = _SCALED.lookup((ent, row_div), ())
+    if sc is not None:
+        return sc
     if ent.is_cuda and torch.cuda.is_current_stream_capturing():
         # a hipGraph capture records kernels without running them: a copy built here would
         # be cached before it holds anything, so the caller keeps the G / row_div route
         return None
-    sc = torch.empty_like(ent)
-    dev = ent.device
-    n_runs = tile_ent.numel() - 1
-    with _on(dev):
-        _capi.check(_lib().maxk_pull_entries_scale(
-            _ptr(ent), _ptr(tiles), _ptr(tile_ent), n_runs, num_rows, num_cols, shift, S,
-            _ptr(row_div), _ptr(sc), _stream(dev)), "maxk_pull_entries_scale")
-    if key not in _SCALED:
-        weakref.finalize(ent, _SCALED.pop, key, None)
-    _SCALED[key] = (weakref.ref(ent), weakref.ref(row_div), _ver(row_div), sc)
-    return sc
+
+    def build():
+        sc = torch.empty_like(ent)
+        _launch(ent.device, "maxk_pull_entries_scale", _ptr(ent), _ptr(tiles), _ptr(tile_ent),
+                tile_ent.numel() - 1, num_rows, num_cols, shift, S, _ptr(row_div), _ptr(sc),
+                _stream(ent.device))
+        return sc
+    return _SCALED.get((ent, row_div), (), build)
 
 
 def _prescale() -> bool:
@@ -682,29 +584,17 @@ def pull_locality(indptr: torch.Tensor, indices: torch.Tensor, shift: int) -> fl
     many more, whatever the average.  One pass over the edges (columns sorted within rows,
     else an under-estimate), cached per (indptr, indices, shift) and their versions.  Reported
     by bench.py (extra.pull_locality); on sparse graphs it steers mode "auto" to "hybrid"."""
-    key = (id(indptr), id(indices), int(shift))
-    hit = _LOCALITY.get(key)
-    if hit is not None:
-        rp, ri, pv, iv, val = hit
-        if rp() is indptr and ri() is indices and pv == _ver(indptr) and \
-                iv == _ver(indices):
-            return val
-    _need(indptr, "indptr", torch.int32)
-    _need(indices, "indices", torch.int32)
-    dev = indices.device
-    out = ctypes.c_double(0.0)
-    ws = torch.empty(8, dtype=torch.uint8, device=dev)
-    with _on(dev):
-        _capi.check(_lib().maxk_pull_locality(_ptr(indptr), _ptr(indices), indptr.numel() - 1,
-                                              indices.numel(), int(shift), ctypes.byref(out),
-                                              _ptr(ws), ws.numel(), _stream(dev)),
-                    "maxk_pull_locality")
-    val = float(out.value)
-    if key not in _LOCALITY:
-        weakref.finalize(indices, _LOCALITY.pop, key, None)
-    _LOCALITY[key] = (weakref.ref(indptr), weakref.ref(indices), _ver(indptr),
-                      _ver(indices), val)
-    return val
+    def build():
+        _need(indptr, "indptr", torch.int32)
+        _need(indices, "indices", torch.int32)
+        dev = indices.device
+        out = ctypes.c_double(0.0)
+        ws = torch.empty(8, dtype=torch.uint8, device=dev)
+        _launch(dev, "maxk_pull_locality", _ptr(indptr), _ptr(indices), indptr.numel() - 1,
+                indices.numel(), int(shift), ctypes.byref(out), _ptr(ws), ws.numel(),
+                _stream(dev))
+        return float(out.value)
+    return _LOCALITY.get((indptr, indices), (int(shift),), build)
 
 
 def _bwd_mode(mode: Optional[str], k: int = 4, num_e: int = 0, num_cols: int = 0,
@@ -742,19 +632,28 @@ def _bwd_mode(mode: Optional[str], k: int = 4, num_e: int = 0, num_cols: int = 0
             loc = pull_locality(graph[0], graph[1], int(L.maxk_pull_shift(int(k))))
             code = int(L.maxk_backward_mode_auto(rows, num_cols, num_e, D, int(k), loc))
         mode = _MODE_OF_CODE[code]
-    if mode == "bsort" and k % 4 != 0:
-        raise RuntimeError(f"backward mode '{mode}' needs k % 4 == 0, got k={k}")
-    if mode == "pull" and k % 4 != 0 and k > 64:
-        raise RuntimeError(f"backward mode 'pull' needs k % 4 == 0 or k <= 64, got k={k}")
-    if mode == "pull" and dim is not None and dim % 4 != 0:
-        raise RuntimeError(f"backward mode 'pull' needs dim_origin % 4 == 0, got {dim}")
-    if mode == "dense" and (k % 4 != 0 or (dim is not None and dim % 4 != 0)):
-        raise RuntimeError(f"backward mode 'dense' needs k % 4 == 0 and dim_origin % 4 == 0, "
-                           f"got k={k}, dim={dim}")
-    if mode == "hybrid" and (k % 4 != 0 or (dim is not None and dim % 4 != 0)):
-        raise RuntimeError(f"backward mode 'hybrid' needs k % 4 == 0 and dim_origin % 4 == 0, "
-                           f"got k={k}, dim={dim}")
+    for ok, message in _MODE_NEEDS.get(mode, ()):
+        if not ok(k, dim):
+            raise RuntimeError(message.format(k=k, dim=dim))
     return mode
+
+
+def _k4_dim4(k, dim):
+    return k % 4 == 0 and (dim is None or dim % 4 == 0)
+
+
+# mode -> ((what (k, dim) must satisfy, the error otherwise), ...); dim None: not known here
+_MODE_NEEDS = {
+    "bsort": ((lambda k, dim: k % 4 == 0, "backward mode 'bsort' needs k % 4 == 0, got k={k}"),),
+    "pull": ((lambda k, dim: k % 4 == 0 or k <= 64,
+              "backward mode 'pull' needs k % 4 == 0 or k <= 64, got k={k}"),
+             (lambda k, dim: dim is None or dim % 4 == 0,
+              "backward mode 'pull' needs dim_origin % 4 == 0, got {dim}")),
+    "dense": ((_k4_dim4, "backward mode 'dense' needs k % 4 == 0 and dim_origin % 4 == 0, "
+                         "got k={k}, dim={dim}"),),
+    "hybrid": ((_k4_dim4, "backward mode 'hybrid' needs k % 4 == 0 and dim_origin % 4 == 0, "
+                          "got k={k}, dim={dim}"),),
+}
 
 
 def backward_plan(indices: torch.Tensor, num_cols: int, k: int, mode: Optional[str] = None,
@@ -796,7 +695,8 @@ def sspmm_backward(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Te
     selectors per edge (edge_selectors(), or the forward's by-product), read in CSR order
     instead of gathered.
 
-    mode "auto" (default; MAXK_BWD_MODE overrides): "pull", "hybrid" or "csc", see _bwd_mode.
+    mode "auto" (default; MAXK_BWD_MODE overrides): "dense", "pull", "hybrid", "bsort" or
+    "csc", see _bwd_mode.
     mode "pull": per tile (row slice, destination bucket), the k values of every edge
     gathered from G and summed in fp64 LDS accumulators, no contribution rows (with a
     row_div the plan's weights are pre-divided, once per divisor: _scaled_entries);
@@ -838,141 +738,133 @@ def sspmm_backward(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Te
         _need(out, "out", torch.float32)
         if tuple(out.shape) != (num_cols, k):
             raise RuntimeError("out must be [num_cols, k]")
-    L = _lib()
     E = indices.numel()
     asked = mode or os.environ.get("MAXK_BWD_MODE", "auto")
     mode = _bwd_mode(mode, k, E, num_cols, num_rows, D, (indptr, indices))
-    if mode == "dense":
-        aligned = (grad_output.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
-                   and cbsr_idx.data_ptr() % 4 == 0)
-        if not aligned and asked == "auto":
-            mode, plan = "pull", None  # the dense kernels' vector loads need aligned rows
-    if mode == "dense":
-        col_ptr, t_src, t_w = (plan if plan is not None
-                               else dense_plan(indptr, indices, values, num_cols))
-        ws_bytes = L.maxk_sspmm_backward_dense_workspace_size(num_rows, num_cols, E, D, k, chunk)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        with _on(dev):
-            _capi.check(L.maxk_sspmm_backward_dense(
-                _ptr(col_ptr), _ptr(t_src), _ptr(t_w), _ptr(grad_output), _ptr(row_div),
-                _ptr(cbsr_idx), _ptr(out), num_rows, num_cols, E, D, k, chunk, _ptr(ws),
-                ws.numel(), _stream(dev)), "maxk_sspmm_backward_dense")
-        return out
-    if mode == "hybrid":
-        tl, te, bp, bt, ent, shift, S, off = (plan if plan is not None else
-                                             hybrid_plan(indptr, indices, values, num_cols, k, D))
-        oip, oix, oval, (ocp, oeid) = off
-        n_t = tl.numel()
-        flags = 0
-        if row_div is not None and n_t > 0 and _prescale():
-            sc = _scaled_entries(ent, tl, te, num_rows, num_cols, shift, S, row_div)
-            if sc is not None:
-                ent, flags = sc, MAXK_HYBRID_PRESCALED
-        ws_bytes = L.maxk_sspmm_backward_hybrid_workspace_size(num_rows, num_cols, oix.numel(),
-                                                               D, k, n_t)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        with _on(dev):
-            overlap = (oix.numel() > 0 and n_t > 0
-                       and os.environ.get("MAXK_HYBRID_STREAMS", "1") != "0")
-            if not overlap:  # everything on the caller's stream, in one C-ABI call
-                _capi.check(L.maxk_sspmm_backward_hybrid(
-                    _ptr(grad_output), _ptr(row_div), _ptr(cbsr_idx), _ptr(tl), _ptr(te), n_t,
-                    _ptr(bp), _ptr(bt), _ptr(ent), ent.shape[0], shift, S, _ptr(oip), _ptr(oix),
-                    _ptr(oval), oix.numel(), _ptr(ocp), _ptr(oeid), flags, _ptr(out), num_rows,
-                    num_cols, D, k, _ptr(ws), ws.numel(), _stream(dev), None, None, None),
-                    "maxk_sspmm_backward_hybrid")
-                return out
-            # the same sequence with the tile kernels on a side stream beside the csc, forked
-            # and joined by torch (fresh events each call: one pair re-recorded by eager calls
-            # broke the join of a graph captured with it, test_hipgraph_capture_*[hybrid])
-            a = L.maxk_sspmm_backward_csc_workspace_size(num_rows, num_cols, oix.numel(), D, k, 0)
-            a = (a + 255) // 256 * 256
-            ws_csc, ws_pull = ws[:a], ws[a:]
-            tile_div = None if flags & MAXK_HYBRID_PRESCALED else row_div
-
-            def tiles(acc, stream):
-                _capi.check(L.maxk_sspmm_backward_pull_tiles(
-                    _ptr(grad_output), _ptr(tile_div), _ptr(cbsr_idx), _ptr(tl), _ptr(te), n_t,
-                    _ptr(bp), _ptr(bt), _ptr(ent), shift, S, acc, _ptr(out), num_rows, num_cols,
-                    ent.shape[0], D, k, _ptr(ws_pull), ws_pull.numel(), stream),
-                    "maxk_sspmm_backward_pull_tiles")
-            main = torch.cuda.current_stream(dev)
-            side = _side_stream(dev)
-            side.wait_stream(main)
-            tiles(MAXK_PULL_NO_REDUCE, ctypes.c_void_p(side.cuda_stream))
-            _capi.check(L.maxk_sspmm_backward_csc(
-                _ptr(oip), _ptr(oix), _ptr(oval), _ptr(grad_output), _ptr(row_div),
-                _ptr(cbsr_idx), _ptr(ocp), _ptr(oeid), _ptr(out), num_rows, num_cols, oix.numel(),
-                D, k, 0, _ptr(ws_csc), ws_csc.numel(), _stream(dev)), "maxk_sspmm_backward_csc")
-            main.wait_stream(side)
-            tiles(MAXK_PULL_REDUCE_ONLY | 1, _stream(dev))
-        # the side stream is joined to the caller's stream before the call returns, so what
-        # it read (ws included) is free for reuse in that stream's order
-        return out
-    if mode == "pull":
-        tptr, ent, shift, S = (plan if plan is not None else
-                               pull_plan(indptr, indices, values, num_cols, k, D))
-        if row_div is not None and E > 0 and _prescale():
-            sc = _scaled_entries(ent, None, tptr, num_rows, num_cols, shift, S, row_div)
-            if sc is not None:
-                ent, row_div = sc, None
-        ws_bytes = L.maxk_sspmm_backward_pull_workspace_size(num_rows, num_cols, D, k, S)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        with _on(dev):
-            _capi.check(L.maxk_sspmm_backward_pull(
-                _ptr(grad_output), _ptr(row_div), _ptr(cbsr_idx), _ptr(tptr), _ptr(ent), shift,
-                S, _ptr(out), num_rows, num_cols, E, D, k, _ptr(ws), ws.numel(), _stream(dev)),
-                "maxk_sspmm_backward_pull")
-        return out
-    if mode == "bsort":
-        if k > BSORT_KMAX and (id(indptr), k) not in _BSORT_WARNED:
-            _BSORT_WARNED.add((id(indptr), k))
-            warnings.warn(f"backward mode 'bsort' at k={k} > {BSORT_KMAX} (MAXK_BSORT_KMAX): a "
-                          f"window of {int(L.maxk_bsort_window(k))} edges holds few rows per "
-                          "destination bucket; correct, but csc is faster", stacklevel=2)
-        bptr, bpos, bdst, wsrc, wrow, shift = (plan if plan is not None
-                                               else bsort_plan(indptr, indices, num_cols, k))
-        if edge_sel is not None:
-            _need(edge_sel, "edge_sel", torch.uint8)
-            if tuple(edge_sel.shape) != (E, k):
-                raise RuntimeError("edge_sel must be [num_e, k]")
-        ws_bytes = L.maxk_sspmm_backward_bsort_workspace_size(num_rows, num_cols, E, D, k)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        with _on(dev):
-            _capi.check(L.maxk_sspmm_backward_bsort(
-                _ptr(indptr), _ptr(indices), _ptr(values), _ptr(grad_output), _ptr(row_div),
-                _ptr(cbsr_idx), _ptr(edge_sel), _ptr(bptr), _ptr(bpos), _ptr(bdst), _ptr(wsrc),
-                _ptr(wrow), shift, _ptr(out), num_rows, num_cols, E, D, k, _ptr(ws), ws.numel(),
-                _stream(dev)), "maxk_sspmm_backward_bsort")
-        return out
-    if mode == "atomic":
-        ws_bytes = L.maxk_sspmm_backward_workspace_size(num_rows, num_cols, E, D, k, chunk)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        with _on(dev):
-            _capi.check(L.maxk_sspmm_backward(
-                _ptr(indptr), _ptr(indices), _ptr(values), _ptr(grad_output), _ptr(row_div),
-                _ptr(cbsr_idx), _ptr(out), num_rows, num_cols, E, D, k, chunk, _ptr(ws),
-                ws.numel(), _stream(dev)), "maxk_sspmm_backward")
-        return out
-    col_ptr, csc_eid = plan if plan is not None else transpose_plan(indices, num_cols)
-    ws_bytes = L.maxk_sspmm_backward_csc_workspace_size(num_rows, num_cols, E, D, k, chunk)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    if edge_sel is not None:
+    if mode == "dense" and asked == "auto" and not (
+            grad_output.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+            and cbsr_idx.data_ptr() % 4 == 0):
+        mode, plan = "pull", None  # the dense kernels' vector loads need aligned rows
+    if edge_sel is not None and mode in ("csc", "bsort"):
         _need(edge_sel, "edge_sel", torch.uint8)
         if tuple(edge_sel.shape) != (E, k):
             raise RuntimeError("edge_sel must be [num_e, k]")
-        with _on(dev):
-            _capi.check(L.maxk_sspmm_backward_csc_sel(
-                _ptr(indptr), _ptr(indices), _ptr(values), _ptr(grad_output), _ptr(row_div),
-                _ptr(edge_sel), _ptr(col_ptr), _ptr(csc_eid), _ptr(out), num_rows, num_cols, E,
-                D, k, chunk, _ptr(ws), ws.numel(), _stream(dev)), "maxk_sspmm_backward_csc_sel")
-        return out
-    with _on(dev):
-        _capi.check(L.maxk_sspmm_backward_csc(
-            _ptr(indptr), _ptr(indices), _ptr(values), _ptr(grad_output), _ptr(row_div),
-            _ptr(cbsr_idx), _ptr(col_ptr), _ptr(csc_eid), _ptr(out), num_rows, num_cols, E, D,
-            k, chunk, _ptr(ws), ws.numel(), _stream(dev)), "maxk_sspmm_backward_csc")
+    _BWD[mode](indptr, indices, values, grad_output, row_div, cbsr_idx, edge_sel, out,
+               (num_rows, num_cols, E, D, k), chunk, plan)
     return out
+
+
+# One function per backward mode, all called as _BWD[mode](indptr, indices, values, G, row_div,
+# sel, edge_sel, out, shape, chunk, plan) with shape = (num_rows, num_cols, E, D, k) and every
+# operand checked by sspmm_backward; `plan` None: the graph's cached plan.
+def _bwd_dense(indptr, indices, values, G, row_div, sel, edge_sel, out, shape, chunk, plan):
+    col_ptr, t_src, t_w = (plan if plan is not None
+                           else dense_plan(indptr, indices, values, shape[1]))
+    _launch_ws(G.device, "maxk_sspmm_backward_dense", "maxk_sspmm_backward_dense_workspace_size",
+               (*shape, chunk),
+               (_ptr(col_ptr), _ptr(t_src), _ptr(t_w), _ptr(G), _ptr(row_div), _ptr(sel),
+                _ptr(out), *shape, chunk))
+
+
+def _bwd_hybrid(indptr, indices, values, G, row_div, sel, edge_sel, out, shape, chunk, plan):
+    num_rows, num_cols, _, D, k = shape
+    tl, te, bp, bt, ent, shift, S, off = (plan if plan is not None else
+                                         hybrid_plan(indptr, indices, values, num_cols, k, D))
+    oip, oix, oval, (ocp, oeid) = off
+    n_t, n_off = tl.numel(), oix.numel()
+    flags = 0
+    if row_div is not None and n_t > 0 and _prescale():
+        sc = _scaled_entries(ent, tl, te, num_rows, num_cols, shift, S, row_div)
+        if sc is not None:
+            ent, flags = sc, MAXK_HYBRID_PRESCALED
+    dev = G.device
+    size = "maxk_sspmm_backward_hybrid_workspace_size", (num_rows, num_cols, n_off, D, k, n_t)
+    if not (n_off > 0 and n_t > 0 and os.environ.get("MAXK_HYBRID_STREAMS", "1") != "0"):
+        # everything on the caller's stream, in one C-ABI call
+        _launch_ws(dev, "maxk_sspmm_backward_hybrid", *size,
+                   (_ptr(G), _ptr(row_div), _ptr(sel), _ptr(tl), _ptr(te), n_t, _ptr(bp), _ptr(bt),
+                    _ptr(ent), ent.shape[0], shift, S, _ptr(oip), _ptr(oix), _ptr(oval), n_off,
+                    _ptr(ocp), _ptr(oeid), flags, _ptr(out), num_rows, num_cols, D, k),
+                   (None, None, None))
+        return
+    # the same sequence with the tile kernels on a side stream beside the csc, forked
+    # and joined by torch (fresh events each call: one pair re-recorded by eager calls
+    # broke the join of a graph captured with it, test_hipgraph_capture_*[hybrid])
+    with _on(dev):
+        ws = _workspace(dev, size[0], *size[1])
+        a = _sized(dev, "maxk_sspmm_backward_csc_workspace_size", num_rows, num_cols, n_off, D,
+                   k, 0)
+        a = (a + 255) // 256 * 256
+        ws_csc, ws_pull = ws[:a], ws[a:]
+        tile_div = None if flags & MAXK_HYBRID_PRESCALED else row_div
+
+        def tiles(acc, stream):
+            _launch(dev, "maxk_sspmm_backward_pull_tiles", _ptr(G), _ptr(tile_div), _ptr(sel),
+                    _ptr(tl), _ptr(te), n_t, _ptr(bp), _ptr(bt), _ptr(ent), shift, S, acc,
+                    _ptr(out), num_rows, num_cols, ent.shape[0], D, k, _ptr(ws_pull),
+                    ws_pull.numel(), stream)
+        main = torch.cuda.current_stream(dev)
+        side = _side_stream(dev)
+        side.wait_stream(main)
+        tiles(MAXK_PULL_NO_REDUCE, ctypes.c_void_p(side.cuda_stream))
+        _launch(dev, "maxk_sspmm_backward_csc", _ptr(oip), _ptr(oix), _ptr(oval), _ptr(G),
+                _ptr(row_div), _ptr(sel), _ptr(ocp), _ptr(oeid), _ptr(out), num_rows, num_cols,
+                n_off, D, k, 0, _ptr(ws_csc), ws_csc.numel(), _stream(dev))
+        main.wait_stream(side)
+        tiles(MAXK_PULL_REDUCE_ONLY | 1, _stream(dev))
+    # the side stream is joined to the caller's stream before the call returns, so what
+    # it read (ws included) is free for reuse in that stream's order
+
+
+def _bwd_pull(indptr, indices, values, G, row_div, sel, edge_sel, out, shape, chunk, plan):
+    num_rows, num_cols, E, D, k = shape
+    tptr, ent, shift, S = (plan if plan is not None else
+                           pull_plan(indptr, indices, values, num_cols, k, D))
+    if row_div is not None and E > 0 and _prescale():
+        sc = _scaled_entries(ent, None, tptr, num_rows, num_cols, shift, S, row_div)
+        if sc is not None:
+            ent, row_div = sc, None
+    _launch_ws(G.device, "maxk_sspmm_backward_pull", "maxk_sspmm_backward_pull_workspace_size",
+               (num_rows, num_cols, D, k, S),
+               (_ptr(G), _ptr(row_div), _ptr(sel), _ptr(tptr), _ptr(ent), shift, S, _ptr(out),
+                *shape))
+
+
+def _bwd_bsort(indptr, indices, values, G, row_div, sel, edge_sel, out, shape, chunk, plan):
+    k = shape[4]
+    if k > BSORT_KMAX and (id(indptr), k) not in _BSORT_WARNED:
+        _BSORT_WARNED.add((id(indptr), k))
+        warnings.warn(f"backward mode 'bsort' at k={k} > {BSORT_KMAX} (MAXK_BSORT_KMAX): a "
+                      f"window of {int(_lib().maxk_bsort_window(k))} edges holds few rows per "
+                      "destination bucket; correct, but csc is faster", stacklevel=3)
+    bptr, bpos, bdst, wsrc, wrow, shift = (plan if plan is not None
+                                           else bsort_plan(indptr, indices, shape[1], k))
+    _launch_ws(G.device, "maxk_sspmm_backward_bsort", "maxk_sspmm_backward_bsort_workspace_size",
+               shape,
+               (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(G), _ptr(row_div), _ptr(sel),
+                _ptr(edge_sel), _ptr(bptr), _ptr(bpos), _ptr(bdst), _ptr(wsrc), _ptr(wrow), shift,
+                _ptr(out), *shape))
+
+
+def _bwd_atomic(indptr, indices, values, G, row_div, sel, edge_sel, out, shape, chunk, plan):
+    _launch_ws(G.device, "maxk_sspmm_backward", "maxk_sspmm_backward_workspace_size",
+               (*shape, chunk),
+               (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(G), _ptr(row_div), _ptr(sel),
+                _ptr(out), *shape, chunk))
+
+
+def _bwd_csc(indptr, indices, values, G, row_div, sel, edge_sel, out, shape, chunk, plan):
+    col_ptr, csc_eid = plan if plan is not None else transpose_plan(indices, shape[1])
+    name = "maxk_sspmm_backward_csc"
+    if edge_sel is not None:  # the per-edge selectors take the selector table's place
+        name, sel = name + "_sel", edge_sel
+    _launch_ws(G.device, name, "maxk_sspmm_backward_csc_workspace_size", (*shape, chunk),
+               (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(G), _ptr(row_div), _ptr(sel),
+                _ptr(col_ptr), _ptr(csc_eid), _ptr(out), *shape, chunk))
+
+
+_BWD = {"dense": _bwd_dense, "hybrid": _bwd_hybrid, "pull": _bwd_pull, "bsort": _bwd_bsort,
+        "atomic": _bwd_atomic, "csc": _bwd_csc}
 
 
 EDGE_SEL_KMAX = 16
@@ -1022,9 +914,8 @@ def edge_selectors(indices: torch.Tensor, cbsr_idx: torch.Tensor,
     E, k = indices.numel(), cbsr_idx.shape[1]
     if out is None:
         out = torch.empty(E, k, dtype=torch.uint8, device=indices.device)
-    with torch.cuda.device(indices.device):
-        _capi.check(_lib().maxk_edge_selectors(_ptr(indices), _ptr(cbsr_idx), E, k, _ptr(out),
-                                               _stream(indices.device)), "maxk_edge_selectors")
+    _launch(indices.device, "maxk_edge_selectors", _ptr(indices), _ptr(cbsr_idx), E, k, _ptr(out),
+            _stream(indices.device))
     return out
 
 
@@ -1073,17 +964,15 @@ def topk_cbsr(x: torch.Tensor, k: int, with_int32: bool = False):
     val = torch.empty(V, k, dtype=x.dtype, device=dev)
     idx = torch.empty(V, k, dtype=torch.uint8, device=dev)
     idx32 = torch.empty(V, k, dtype=torch.int32, device=dev) if with_int32 else None
-    L = _lib()
     if x.dtype == torch.float32:
-        fn, name = L.maxk_topk_cbsr, "maxk_topk_cbsr"
+        name = "maxk_topk_cbsr"
     elif x.dtype == torch.uint8:
-        fn, name = L.maxk_topk_cbsr_u8, "maxk_topk_cbsr_u8"
+        name = "maxk_topk_cbsr_u8"
     else:
         raise RuntimeError("Input must be float32 or uint8")
     check = _checks_topk_rows(dev)
-    with _on(dev):
-        _capi.check(fn(_ptr(x), x.stride(0), _ptr(val), _ptr(idx), _ptr(idx32), V, D, k,
-                       _stream(dev)), name)
+    _launch(dev, name, _ptr(x), x.stride(0), _ptr(val), _ptr(idx), _ptr(idx32), V, D, k,
+            _stream(dev))
     if check:
         _check_topk_rows(dev, name)
     return (val, idx, idx32) if with_int32 else (val, idx)
@@ -1096,9 +985,7 @@ def topk_error_rows(device=None, reset: bool = True) -> int:
     inside its own k winner slots."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     n = ctypes.c_int64(0)
-    with _on(dev):
-        _capi.check(_lib().maxk_topk_error_rows(ctypes.byref(n), 1 if reset else 0,
-                                                _stream(dev)), "maxk_topk_error_rows")
+    _launch(dev, "maxk_topk_error_rows", ctypes.byref(n), 1 if reset else 0, _stream(dev))
     return int(n.value)
 
 
@@ -1136,9 +1023,8 @@ def topk_u8_reference(input: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.
     N = input.shape[0]
     val = torch.empty(N, k, dtype=torch.uint8, device=input.device)
     idx = torch.empty(N, k, dtype=torch.uint8, device=input.device)
-    with _on(input.device):
-        _capi.check(_lib().maxk_topk_u8_reference(_ptr(input), _ptr(val), _ptr(idx), N, 256, int(k),
-                                                  _stream(input.device)), "maxk_topk_u8_reference")
+    _launch(input.device, "maxk_topk_u8_reference", _ptr(input), _ptr(val), _ptr(idx), N, 256,
+            int(k), _stream(input.device))
     return val, idx
 
 
@@ -1192,10 +1078,8 @@ def cbsr_scatter_dense(cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor, dim_origi
     dev = cbsr_val.device
     if out is None:
         out = torch.empty(V, dim_origin, dtype=torch.float32, device=dev)
-    with _on(dev):
-        _capi.check(_lib().maxk_cbsr_scatter_dense(_ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), V,
-                                                   dim_origin, k, _stream(dev)),
-                    "maxk_cbsr_scatter_dense")
+    _launch(dev, "maxk_cbsr_scatter_dense", _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), V,
+            dim_origin, k, _stream(dev))
     return out
 
 
@@ -1216,10 +1100,8 @@ def topk_cbsr_dense(x: torch.Tensor, k: int):
     idx = torch.empty(V, k, dtype=torch.uint8, device=dev)
     dense = torch.empty(V, D, dtype=torch.float32, device=dev)
     check = _checks_topk_rows(dev)
-    with _on(dev):
-        _capi.check(_lib().maxk_topk_cbsr_dense(_ptr(x), x.stride(0), _ptr(val), _ptr(idx),
-                                                _ptr(dense), V, D, k, _stream(dev)),
-                    "maxk_topk_cbsr_dense")
+    _launch(dev, "maxk_topk_cbsr_dense", _ptr(x), x.stride(0), _ptr(val), _ptr(idx), _ptr(dense),
+            V, D, k, _stream(dev))
     if check:
         _check_topk_rows(dev, "maxk_topk_cbsr_dense")
     return dense, val, idx
@@ -1248,10 +1130,8 @@ def topk_backward(grad_val: Optional[torch.Tensor], grad_dense: Optional[torch.T
         _need(out, "out", torch.float32)
         if tuple(out.shape) != (V, dim_origin):
             raise RuntimeError("out must be [V, dim_origin]")
-    with _on(dev):
-        _capi.check(_lib().maxk_topk_backward(_ptr(grad_val), _ptr(grad_dense), _ptr(cbsr_idx),
-                                              _ptr(out), V, dim_origin, k, _stream(dev)),
-                    "maxk_topk_backward")
+    _launch(dev, "maxk_topk_backward", _ptr(grad_val), _ptr(grad_dense), _ptr(cbsr_idx), _ptr(out),
+            V, dim_origin, k, _stream(dev))
     return out
 
 
@@ -1279,11 +1159,9 @@ class DenseSpMMPlan:
         self._keep = (indptr, indices, values)
         self.device = x.device
         h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _capi.check(_lib().maxk_dense_spmm_plan_create(
-                ctypes.byref(h), _ptr(indptr), _ptr(indices), _ptr(values), _ptr(x),
-                _ptr(self.y), self.num_rows, x.shape[0], indices.numel(), x.shape[1], alg,
-                _stream(self.device)), "maxk_dense_spmm_plan_create")
+        _launch(self.device, "maxk_dense_spmm_plan_create", ctypes.byref(h), _ptr(indptr),
+                _ptr(indices), _ptr(values), _ptr(x), _ptr(self.y), self.num_rows, x.shape[0],
+                indices.numel(), x.shape[1], alg, _stream(self.device))
         self._h = h
 
     def run(self, x: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None
@@ -1296,12 +1174,9 @@ class DenseSpMMPlan:
             _need(y, "y", torch.float32)
             if tuple(x.shape) != tuple(self.x.shape) or tuple(y.shape) != tuple(self.y.shape):
                 raise RuntimeError("rebound x / y must keep the plan's shapes")
-            _capi.check(_lib().maxk_dense_spmm_bind(self._h, _ptr(x), _ptr(y)),
-                        "maxk_dense_spmm_bind")
+            _launch(self.device, "maxk_dense_spmm_bind", self._h, _ptr(x), _ptr(y))
             self.x, self.y = x, y
-        with torch.cuda.device(self.device):
-            _capi.check(_lib().maxk_dense_spmm_run(self._h, _stream(self.device)),
-                        "maxk_dense_spmm_run")
+        _launch(self.device, "maxk_dense_spmm_run", self._h, _stream(self.device))
         return self.y
 
     def close(self):
