@@ -31,6 +31,17 @@
  * unselected zeros by the weight).  The forward (every form) and the csc and dense backwards
  * sum in a fixed order: bitwise repeatable, and bitwise equivariant under a power-of-two scale
  * of the values away from overflow and underflow.
+ *
+ * Memory (tests/memguard.py, tests/test_memguard_gpu.py): a workspace, a plan buffer and an
+ * output may hold anything when a call starts -- zeros, 0xFF bytes, what an earlier call left
+ * there -- and nothing needs zero-initialising by the caller; the result does not depend on it
+ * (bitwise, where the sum order is fixed).  A workspace of exactly the documented size (the
+ * call's *_workspace_size query; 8 bytes for maxk_pull_locality; 0, so NULL, for the atomic
+ * maxk_sspmm_backward) is sufficient, and it is required: a shorter one is rejected with
+ * MAXK_ERR_INVALID ("workspace too small") on the host, before anything is launched or written.
+ * Outputs are fully written (an accumulate form's `out` fully updated), inputs are never
+ * written (except where an output is documented to alias one: maxk_topk_backward's grad_x ==
+ * grad_dense), and nothing is written outside the buffers passed, not by a byte.
  */
 #ifndef MAXK_HIP_H_
 #define MAXK_HIP_H_

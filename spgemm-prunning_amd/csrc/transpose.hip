@@ -259,15 +259,19 @@ extern "C" int maxk_bsort_plan(const int32_t *row_ptr, const int32_t *col_idx, i
     MAXK_REQUIRE(nwin * (nb > 0 ? nb : 1) < (1LL << 31),
                  "%lld windows x %lld buckets exceed the 31-bit sort key", (long long)nwin,
                  (long long)nb);
+    // every check of this call before the bucket plan's launches: the bucket plan alone needs
+    // less workspace than the window sort after it, and nothing may be written by a rejected call
+    const size_t need = maxk_bsort_plan_workspace_size(num_cols, num_e);
+    if (num_e > 0) {
+        MAXK_REQUIRE(row_ptr && win_src && edge_row, "row_ptr/win_src/edge_row must not be NULL");
+        MAXK_REQUIRE(num_rows > 0, "edges present but num_rows == 0");
+        MAXK_REQUIRE(workspace && workspace_bytes >= need, "workspace too small: need %zu", need);
+    }
     // the bucket plan, its edge ids landing in bucket_pos (num_e == 0: bucket_ptr zeroed)
     if (int rc = bucket_plan(col_idx, num_cols, num_e, bucket_shift, bucket_ptr, bucket_pos,
                                   bucket_dst, workspace, workspace_bytes, stream))
         return rc;
     if (num_e == 0) return MAXK_OK;
-    MAXK_REQUIRE(row_ptr && win_src && edge_row, "row_ptr/win_src/edge_row must not be NULL");
-    MAXK_REQUIRE(num_rows > 0, "edges present but num_rows == 0");
-    const size_t need = maxk_bsort_plan_workspace_size(num_cols, num_e);
-    MAXK_REQUIRE(workspace && workspace_bytes >= need, "workspace too small: need %zu", need);
     hipStream_t s = as_stream(stream);
     char *ws = reinterpret_cast<char *>(workspace);
     const size_t a = al256((size_t)num_e * 4);

@@ -152,8 +152,11 @@ def check_form(mk, fid, name, D, k):
     assert (E >= 128 * g.R) == (name == "Dn")
 
 
-def run_fwd(mk, name, variant, cv, ci, D, chunk, out=None, accumulate=False, validate=None):
-    rp, col, ev, div = dgraph(name)
+def run_fwd(mk, name, variant, cv, ci, D, chunk, out=None, accumulate=False, validate=None,
+            gt=None, es_out=None):
+    """gt: the graph's device tensors in place of the cached dgraph(name); es_out: the caller's
+    buffer for the emit variant's edge selectors."""
+    rp, col, ev, div = dgraph(name) if gt is None else gt
     k = ci.shape[1]
     if variant == "records":
         rec = mk.cbsr_records(cv, ci, D)
@@ -161,7 +164,9 @@ def run_fwd(mk, name, variant, cv, ci, D, chunk, out=None, accumulate=False, val
                                          out=out, accumulate=accumulate, validate=validate)
     es = None
     if variant == "emit":
-        es = torch.full((col.numel(), k), 0xAB, dtype=torch.uint8, device=DEV)
+        es = es_out
+        if es is None:
+            es = torch.full((col.numel(), k), 0xAB, dtype=torch.uint8, device=DEV)
     y = mk.spgemm_forward(rp, col, ev, cv, ci, D, row_div=div, chunk=chunk, out=out,
                           accumulate=accumulate, validate=validate, edge_sel_out=es)
     if es is not None:
@@ -236,8 +241,8 @@ BWD_IDS = [b[0] for b in BWD]
 BITWISE = [b for b in BWD if b[5] in ("csc", "dense")]
 
 
-def run_bwd(mk, name, G, ci, mode, chunk, extra, validate=None):
-    rp, col, ev, div = dgraph(name)
+def run_bwd(mk, name, G, ci, mode, chunk, extra, validate=None, gt=None):
+    rp, col, ev, div = dgraph(name) if gt is None else gt
     g = graph(name)
     k, D = ci.shape[1], G.shape[1]
     kw = {}
