@@ -275,7 +275,7 @@ int maxk_sspmm_backward_bsort(const int32_t *row_ptr, const int32_t *col_idx,
  * gathered directly, fp64 LDS accumulation, then the slices of a bucket added in slice
  * order.  The fp64 tile sums make two runs agree except in rare rounding ties (bitwise
  * repeatability: maxk_sspmm_backward_csc).  For dim_k % 4 == 0 each destination's selectors
- * are first re-ordered by column (quantile slots, sspmm_bwd.hip pull_sel_kernel) so one
+ * are first re-ordered by column (quantile slots, sspmm_pull.hip pull_sel_kernel) so one
  * gather instruction touches fewer lines of a row; the sums return to CBSR order at the
  * end.  With dim_k % 4 == 0 a tile's destination slots may be split by sorted rank into
  * parts of kp = dim_k / H slots, one workgroup each, so a bucket holds H times the

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "maxk_hip.h"
 
@@ -68,10 +69,19 @@ constexpr int kBucketAccDoubles = 18432;
 #define MAXK_PULL_SHIFT_DELTA 0
 #endif
 constexpr size_t kPullLdsBytes = 160 * 1024;  // LDS of one workgroup on gfx950
+// pull_q_kernel's LDS use and fit rule: a bucket of 2^shift destinations with kp slots each
+// holds, per destination, an fp64 accumulator row of ks doubles (kp, or kp + 1 padded) and kp
+// selector bytes
+__host__ __device__ inline size_t pull_lds_bytes(int ks, int kp, int shift) {
+    return ((size_t)ks * 8 + kp) << shift;
+}
+__host__ __device__ inline bool pull_fits(int ks, int kp, int shift) {
+    return pull_lds_bytes(ks, kp, shift) <= kPullLdsBytes;
+}
 // pull_q_kernel accumulator row stride in doubles: kp + 1 (the pad spreads a wave's
 // destinations over the LDS banks) when the padded bucket fits, else kp
 __host__ __device__ inline int pull_ks(int kp, int shift) {
-    return ((((size_t)(kp + 1) * 8 + kp) << shift) <= kPullLdsBytes) ? kp + 1 : kp;
+    return pull_fits(kp + 1, kp, shift) ? kp + 1 : kp;
 }
 #ifndef MAXK_PULL_SHFL  // pull: the step's entries by one load + lane shuffles
 #define MAXK_PULL_SHFL 1
@@ -235,6 +245,32 @@ void clear_error();
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Every piece of a workspace starts on a 256-B boundary: sizes are rounded up with this.
+inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+
+// ---- kernel dispatch: a run-time value as a compile-time constant ----
+// Calls f(std::integral_constant<int, V>{}) for the V among Vs equal to v and returns true;
+// returns false, f not called, when none is.  f is a generic lambda whose body launches the
+// kernel instantiated for V: each V compiles that body once, so a launch site instantiates
+// exactly the variants it lists.  A combination a site never launches is kept out of a nested
+// dispatch with `if constexpr`.
+template <int V>
+using const_t = std::integral_constant<int, V>;
+template <int... Vs, class F>
+bool with_const(int v, F &&f) {
+    return ((v == Vs && (f(const_t<Vs>{}), true)) || ...);
+}
+// ... over the lane groups (lanes_per_edge): the powers of two up to a wave
+template <class F>
+bool with_lanes(int v, F &&f) {
+    return with_const<1, 2, 4, 8, 16, 32, 64>(v, f);
+}
+// what a launch site returns when with_lanes / with_const matched nothing
+inline int bad_lanes(int lanes) {
+    set_error("unsupported lane group %d", lanes);
+    return MAXK_ERR_INVALID;
+}
 
 // CUs of the current device (hipDeviceAttributeMultiprocessorCount), cached per device ordinal:
 // the grid and work-item sizing of every launch scales with it.  256 (MI355X) when no device

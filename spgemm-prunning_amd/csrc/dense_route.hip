@@ -33,8 +33,6 @@ constexpr int kDenseLdsWords = 4096;  // its LDS rows: (4 * kDenseBlock / k) * D
 constexpr int kDenseGroupMax = 64;   // rows of at most this many item edges go to lane groups
 constexpr int kDenseChunkMax = 512;  // item size cap (LDS staging: 8 B per token per wave)
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // X[v, :] = the dense row of vertex v's CBSR: four l per thread (one u32 selector word, one
 // float4 of values), 4 * kDenseBlock / k whole vertices per group, rows assembled in LDS and
 // stored as one contiguous run.  Duplicate selectors of a vertex: the lowest l carries the sum
@@ -687,30 +685,19 @@ int launch_dense_rows(const DenseLayout &L, hipStream_t s, const int32_t *ptr, c
     const bool select = sel != nullptr;
     const size_t lds = (size_t)kWavesPerBlock * (L.chunk * 16 + (select ? 16 * kWave : 0));
     constexpr int U = MAXK_DENSE_U;
-    switch (dense_lanes(D)) {
-#define MAXK_CASE(LRV)                                                                          \
-    case LRV:                                                                                   \
-        if (select)                                                                             \
-            hipLaunchKernelGGL((dense_select_rows_kernel<LRV, U>), grid, dim3(kBlock), lds, s,  \
-                               ptr, idx, w, src_div, X, D, out, slab, slab_row, rows, num_e,    \
-                               L.chunk, L.n_items, sel, grad_cbsr, k);                          \
-        else                                                                                    \
-            hipLaunchKernelGGL((dense_rows_kernel<LRV, U>), grid, dim3(kBlock), lds, s, ptr,    \
-                               idx, w, X, D, dst_div, out, add, slab, slab_row, rows, num_e,    \
-                               L.chunk, L.n_items);                                             \
-        break;
-        MAXK_CASE(1)
-        MAXK_CASE(2)
-        MAXK_CASE(4)
-        MAXK_CASE(8)
-        MAXK_CASE(16)
-        MAXK_CASE(32)
-        MAXK_CASE(64)
-#undef MAXK_CASE
-        default:
-            set_error("unsupported dense lane group for D = %d", D);
-            return MAXK_ERR_INVALID;
-    }
+    const int lr = dense_lanes(D);
+    const bool ok = with_lanes(lr, [&](auto lr_c) {
+        constexpr int LR = decltype(lr_c)::value;
+        if (select)
+            hipLaunchKernelGGL((dense_select_rows_kernel<LR, U>), grid, dim3(kBlock), lds, s, ptr,
+                               idx, w, src_div, X, D, out, slab, slab_row, rows, num_e, L.chunk,
+                               L.n_items, sel, grad_cbsr, k);
+        else
+            hipLaunchKernelGGL((dense_rows_kernel<LR, U>), grid, dim3(kBlock), lds, s, ptr, idx,
+                               w, X, D, dst_div, out, add, slab, slab_row, rows, num_e, L.chunk,
+                               L.n_items);
+    });
+    if (!ok) return bad_lanes(lr);
     MAXK_LAUNCHED(select ? "dense_select_rows_kernel" : "dense_rows_kernel");
     return MAXK_OK;
 }
@@ -824,25 +811,14 @@ extern "C" int maxk_sspmm_backward_dense(const int32_t *col_ptr, const int32_t *
         const dim3 grid((unsigned)ceil_div(L.n_items, kWavesPerBlock));
         const size_t lds = (size_t)kWavesPerBlock * L.chunk * 16;
         constexpr int U = MAXK_DENSE_U;
-        switch (lanes_per_edge(k)) {
-#define MAXK_CASE(LRV)                                                                         \
-    case LRV:                                                                                  \
-        hipLaunchKernelGGL((pick_rows_kernel<LRV, U>), grid, dim3(kBlock), lds, s, col_ptr,    \
-                           t_src, t_w, row_div, grad_out, D, cbsr_idx, k, grad_cbsr, slab,     \
-                           slab_row, (int)num_cols, num_e, L.chunk, L.n_items);               \
-        break;
-            MAXK_CASE(1)
-            MAXK_CASE(2)
-            MAXK_CASE(4)
-            MAXK_CASE(8)
-            MAXK_CASE(16)
-            MAXK_CASE(32)
-            MAXK_CASE(64)
-#undef MAXK_CASE
-            default:
-                set_error("unsupported lane group for k = %d", k);
-                return MAXK_ERR_INVALID;
-        }
+        const int lr = lanes_per_edge(k);
+        const bool ok = with_lanes(lr, [&](auto lr_c) {
+            hipLaunchKernelGGL((pick_rows_kernel<decltype(lr_c)::value, U>), grid, dim3(kBlock),
+                               lds, s, col_ptr, t_src, t_w, row_div, grad_out, D, cbsr_idx, k,
+                               grad_cbsr, slab, slab_row, (int)num_cols, num_e, L.chunk,
+                               L.n_items);
+        });
+        if (!ok) return bad_lanes(lr);
         MAXK_LAUNCHED("pick_rows_kernel");
         return launch_slab_fixup<1>(slab, slab_row, grad_cbsr, k, L.n_items, s);
     }

@@ -18,8 +18,6 @@
 namespace maxk {
 namespace {
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // flag[t] = tile t is pulled; cnt_d[t] = its entries if pulled, else 0
 __global__ void hybrid_flag_kernel(const int32_t *__restrict__ tile_ptr, int64_t n_tiles, int nb,
                                    int64_t num_rows, int rps, float density,

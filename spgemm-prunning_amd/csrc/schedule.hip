@@ -68,8 +68,6 @@ size_t cub_scan_bytes(int n) {
     return bytes;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 }  // namespace maxk
 
@@ -111,7 +109,7 @@ extern "C" int maxk_warp4_count(const int32_t *row_ptr, int64_t num_rows, int32_
 
 extern "C" size_t maxk_warp4_build_workspace_size(int64_t num_rows) {
     if (num_rows <= 0) return 0;
-    return 2 * align256((size_t)num_rows * sizeof(int32_t)) + align256(cub_scan_bytes((int)num_rows));
+    return 2 * al256((size_t)num_rows * sizeof(int32_t)) + al256(cub_scan_bytes((int)num_rows));
 }
 
 extern "C" int maxk_warp4_build(const int32_t *row_ptr, int64_t num_rows, int32_t warp_max_nz,
@@ -127,9 +125,9 @@ extern "C" int maxk_warp4_build(const int32_t *row_ptr, int64_t num_rows, int32_
     MAXK_REQUIRE(workspace && workspace_bytes >= need, "workspace too small: need %zu", need);
     char *ws = reinterpret_cast<char *>(workspace);
     int32_t *counts = reinterpret_cast<int32_t *>(ws);
-    int32_t *offsets = reinterpret_cast<int32_t *>(ws + align256((size_t)num_rows * 4));
-    void *tmp = ws + 2 * align256((size_t)num_rows * 4);
-    size_t tmp_bytes = align256(cub_scan_bytes((int)num_rows));
+    int32_t *offsets = reinterpret_cast<int32_t *>(ws + al256((size_t)num_rows * 4));
+    void *tmp = ws + 2 * al256((size_t)num_rows * 4);
+    size_t tmp_bytes = al256(cub_scan_bytes((int)num_rows));
     hipStream_t s = as_stream(stream);
     const dim3 grid((unsigned)ceil_div(num_rows, kBlock));
     hipLaunchKernelGGL(warp4_count_kernel, grid, dim3(kBlock), 0, s, row_ptr, (int)num_rows,

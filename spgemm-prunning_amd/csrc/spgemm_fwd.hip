@@ -938,13 +938,12 @@ FwdLayout fwd_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, i
                         fwd_resident_waves(L.kg, L.DS, L.deep ? 4 : L.stream ? 5 : 7));
     const int64_t n = ceil_div(num_rows + num_e, L.chunk);
     L.n_items = (int)(n > 0 ? n : 1);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     L.rec_off = 0;
-    L.rec_bytes = al((size_t)num_cols * L.RS);
+    L.rec_bytes = al256((size_t)num_cols * L.RS);
     L.slab_off = L.rec_off + L.rec_bytes;
-    L.slab_bytes = al((size_t)L.n_items * D * sizeof(float));
+    L.slab_bytes = al256((size_t)L.n_items * D * sizeof(float));
     L.row_off = L.slab_off + L.slab_bytes;
-    L.total = L.row_off + al((size_t)L.n_items * sizeof(int32_t));
+    L.total = L.row_off + al256((size_t)L.n_items * sizeof(int32_t));
     return L;
 }
 
@@ -1105,21 +1104,11 @@ int forward_impl(const int32_t *row_ptr, const int32_t *col_idx, const float *ed
     const bool big = (double)num_rows * D * 4 > (double)kInfinityCacheBytes;
     const int flags = (accumulate ? 1 : 0) |
                       ((MAXK_FWD_OUT_NT == 1 || (MAXK_FWD_OUT_NT == 2 && big)) ? 2 : 0);
-    switch (L.kg) {
-#define MAXK_CASE(KGV)                                                                     \
-    case KGV:                                                                              \
-        launch_fwd<KGV>(L, s, row_ptr, col_idx, edge_val, rec, row_div, out, slab,         \
-                        slab_row, nr, num_e, D, k, flags, esel, trec);                     \
-        break;
-        MAXK_CASE(8)
-        MAXK_CASE(16)
-        MAXK_CASE(32)
-        MAXK_CASE(64)
-#undef MAXK_CASE
-        default:
-            set_error("unsupported lane group %d", L.kg);
-            return MAXK_ERR_INVALID;
-    }
+    const bool ok = with_const<8, 16, 32, 64>(L.kg, [&](auto kg_c) {
+        launch_fwd<decltype(kg_c)::value>(L, s, row_ptr, col_idx, edge_val, rec, row_div, out,
+                                          slab, slab_row, nr, num_e, D, k, flags, esel, trec);
+    });
+    if (!ok) return bad_lanes(L.kg);
     MAXK_LAUNCHED("spgemm_fwd_kernel");
     return launch_slab_fixup<0>(slab, slab_row, out, D, L.n_items, s);
 }

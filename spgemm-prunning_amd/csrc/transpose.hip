@@ -12,8 +12,6 @@
 namespace maxk {
 namespace {
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 __global__ void iota_kernel(int32_t *__restrict__ a, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) a[i] = (int32_t)i;
@@ -382,7 +380,7 @@ extern "C" int maxk_pull_shift(int32_t dim_k) {
         // the widest bucket whose kp-slot rows (unpadded, maxk::pull_ks) and selectors fit
         const int kp = dim_k / H;
         int sh = 0;
-        while (sh < 15 && (((size_t)kp * 8 + kp) << (sh + 1)) <= maxk::kPullLdsBytes) ++sh;
+        while (sh < 15 && maxk::pull_fits(kp, kp, sh + 1)) ++sh;
         s = std::max(s, sh);
     }
     const int p = s - MAXK_PULL_SHIFT_DELTA;

@@ -28,11 +28,12 @@ forward_impl :1045-1097; S is sparse, average degree < kFwdSparseDegree = 128):
   rect       R, 150 x 700.
 
 Sum order, for (b): every forward form is bitwise scale-equivariant.  A product is one fma into
-the lane group's own LDS copy (spgemm_fwd.hip:351, :419, :577, :700; plain ds_read / ds_write,
-no LDS atomics: repeated selectors are folded by the pack, :116-118, :174-181, :248-255), a
-group meets its edges in CSR order, flush_row (:465-514) adds the copies in fixed order and
-slab_fixup_kernel (common.h:382) adds a hub row's slabs in item order; the dense route walks
-rows into registers and uses the same fixup (dense_route.hip:755).  A power-of-two scale
+the lane group's own LDS copy (spgemm_fwd.hip: EdgeWalker, walk_src and stream_rows; plain
+ds_read / ds_write, no LDS atomics: repeated selectors are folded by the pack, cbsr_pack_kernel,
+cbsr_pack4_kernel and cbsr_records_kernel), a group meets its edges in CSR order, flush_row
+adds the copies in fixed order and slab_fixup_kernel (common.h) adds a hub row's slabs in
+item order; the dense route walks rows into registers and uses the same fixup (dense_route.hip,
+dense_forward).  A power-of-two scale
 commutes with every one of these roundings.  Of the backward modes csc, csc with edge_sel= and
 dense are bitwise repeatable (include/maxk_hip.h) and get (b); pull, bsort and hybrid sum
 through order-dependent fp64 LDS atomics and atomic through fp32 global atomics: (a) at both

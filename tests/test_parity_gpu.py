@@ -707,7 +707,10 @@ def run_both(mk, cuda, row_ptr, col, val, cv, ci, g, D, div=None, chunk=0, mode=
 @pytest.mark.parametrize("k,D", [(1, 64), (2, 64), (3, 64), (8, 256), (16, 256), (24, 256),
                                  (32, 256), (48, 256), (64, 256), (96, 256), (128, 256),
                                  (255, 256), (256, 256), (16, 100), (7, 9), (32, 64),
-                                 (64, 64), (52, 100), (64, 128), (128, 128)])
+                                 (64, 64), (52, 100), (64, 128), (128, 128),
+                                 # one lane per edge of the four-per-lane push and csc sum;
+                                 # the pull's one-lane-per-entry form below D = 256
+                                 (4, 256), (8, 64)])
 def test_all_k_against_oracle(mk, cuda, k, D):
     rng = np.random.default_rng(k * 1000 + D)
     V = 600
