@@ -28,8 +28,8 @@
  * values (a NaN behind a selector >= dim_origin or in a vertex no edge reads reaches nothing),
  * and any NaN bit pattern is handled, the transport records' own skip marker included.
  * Non-finite edge weights or row_div are outside the contract (the dense route multiplies
- * unselected zeros by the weight).  The forward (every form) and the csc and dense backwards
- * sum in a fixed order: bitwise repeatable, and bitwise equivariant under a power-of-two scale
+ * unselected zeros by the weight).  The forward (every form), the csc and dense backwards and
+ * the edge-weight gradient sum in a fixed order: bitwise repeatable, and bitwise equivariant under a power-of-two scale
  * of the values away from overflow and underflow.
  *
  * Memory (tests/memguard.py, tests/test_memguard_gpu.py): a workspace, a plan buffer and an
@@ -150,6 +150,42 @@ int maxk_spgemm_forward_records(const int32_t *row_ptr, const int32_t *col_idx,
                                 int32_t dim_origin, int32_t dim_k, int32_t chunk_edges,
                                 void *workspace, size_t workspace_bytes, void *stream,
                                 int32_t accumulate);
+
+/* ---------------------------------------------------------------------------
+ * Gradient of the forward with respect to the edge weights (an SDDMM sampled by the CBSR):
+ *   grad_edge[e] = ( sum_l cbsr_val[c,l] * grad_out[r, cbsr_idx[c,l]] ) / row_div[r]
+ *                  r = the CSR row holding e, c = col_idx[e]
+ * the adjoint of out = diag(1/row_div) . A . scatter(cbsr) in edge_val, which it does not read.
+ * The reference has no counterpart (its autograd returns no gradient for the edge weights).
+ * One packed record gathered per edge, as in the forward; no atomics.
+ * Shapes: any 1 <= dim_k <= dim_origin <= 256 (dim_k % 4 != 0, odd dim_origin, and the pairs
+ *   where the forward takes its dense route: this function has no such route), any alignment
+ *   of grad_out and cbsr_* the plain forward accepts; row_div may be NULL; num_e == 0 launches
+ *   nothing and succeeds.
+ * Numerics, in the words of the top comment: every element is within (n + 8) * 2^-24 *
+ *   sum|terms| of exact arithmetic (plus the (n + 8) * 2^-149 floor for subnormal inputs), n
+ *   the number of column c's selectors below dim_origin; an edge with n = 0 gets exactly 0.
+ *   Inf and NaN in cbsr_val and grad_out propagate as the IEEE sum of the selected terms; a NaN
+ *   behind a selector >= dim_origin, or in a column of grad_out the vertex does not select,
+ *   reaches nothing.  Repeated selectors are summed (their values first, as the forward's pack
+ *   folds them): for them only the finite bound is promised.  The sum order is fixed: bitwise
+ *   repeatable, and bitwise equivariant under a power-of-two scale of cbsr_val or grad_out away
+ *   from overflow and underflow.
+ * Memory, as the top comment: the workspace (the packed records) is exactly the queried size,
+ *   256-B aligned, and may hold anything; a shorter one is rejected with MAXK_ERR_INVALID
+ *   ("workspace too small") on the host before anything is launched; grad_edge [num_e] is fully
+ *   written, in CSR order; inputs are never written; nothing else is touched.
+ * Argument errors (null pointer, k / D range, negative sizes): MAXK_ERR_INVALID with a message.
+ * chunk_edges: tokens per wavefront work item, 0 = the forward's auto rule.
+ * ------------------------------------------------------------------------- */
+size_t maxk_edge_weight_grad_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                            int32_t dim_origin, int32_t dim_k,
+                                            int32_t chunk_edges);
+int maxk_edge_weight_grad(const int32_t *row_ptr, const int32_t *col_idx, const float *cbsr_val,
+                          const uint8_t *cbsr_idx, const float *grad_out, const float *row_div,
+                          float *grad_edge, int64_t num_rows, int64_t num_cols, int64_t num_e,
+                          int32_t dim_origin, int32_t dim_k, int32_t chunk_edges,
+                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Backward outer-product sampled SpMM (SSpMM):

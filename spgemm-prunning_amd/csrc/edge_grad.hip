@@ -1,0 +1,305 @@
+// Gradient of the aggregation with respect to the edge weights, for gfx950: an SDDMM sampled
+// by the CBSR,
+//
+//   grad_edge[e] = ( sum_l cbsr_val[c, l] * G[r, cbsr_idx[c, l]] ) / row_div[r]
+//                  r = the CSR row holding e, c = col_idx[e]
+//
+// the adjoint of out = diag(1/row_div) . A . scatter(cbsr) in A's values.  It shares the
+// forward's gather -- one packed record [k f32 | k u16 | pad] per edge (cbsr_pack.h), so an edge
+// costs one line -- and its token-stream partition (common.h), and nothing else:
+//
+//  1. launch_cbsr_pack writes this call's records into the workspace.  The pack folds repeated
+//     selectors into their first occurrence and sends selectors >= D to the trash column with
+//     value 0, so every term of an edge's dot product is either a kept (value, column < D) pair
+//     or exactly 0 * 0.
+//  2. edge_grad_kernel, one wavefront per item of `chunk` tokens.  An item walks exactly the
+//     edges whose tokens it holds: every edge's result is independent, so a hub row cut over
+//     items needs no slab and no fix-up -- each item stages the row again.
+//     * per row piece: G[r, :] staged once into the wave's LDS row (16-B loads where D % 4 == 0
+//       and grad_out is 16-B aligned, else scalar); the pad columns [D, DS) hold zeros, so a
+//       skipped selector reads 0 even beside a NaN in G;
+//     * per edge: KG = pow2ceil(k) lanes (>= 8, <= 64), G = 64 / KG edges per wave step, U steps
+//       in flight; lane l loads its value and selector through a buffer descriptor
+//       (unconditional: past the piece's end col_idx reads 0, column 0's record, and the result
+//       is not stored), reads G[sel] from LDS and multiplies; for k > 64 a lane accumulates its
+//       slots l, l + 64, ... in l order with one fma each; idle lanes (l >= k) contribute 0;
+//     * a fixed cross-lane tree (DPP quad permutes and mirrors within 16 lanes, ds_swizzle for
+//       the 32-lane step, v_permlane32_swap for the last) sums the group: same order every run;
+//     * the finished dot product is divided by row_div[r] once; a batch's G * U results go
+//       through 64 floats of LDS per wave and leave as one coalesced store in CSR order.
+//       (Lane 0 of each group storing its own result, G consecutive floats per instruction and
+//       U instructions per batch, measured 1.752 against 1.653 ms Reddit-sized at k = 16 and
+//       5.06 against 5.00 ms products-sized at k = 32, the latter inside the run-to-run
+//       spread: MAXK_EGRAD_LDS_STORE=0, profiles/r07/edge_grad/.)
+// No atomics, no allocation, copy or synchronisation: the launch can be captured.
+#include "cbsr_pack.h"
+#include "common.h"
+
+#ifndef MAXK_EGRAD_U  // edge-gradient: wave steps of record loads in flight
+#define MAXK_EGRAD_U 8
+#endif
+#ifndef MAXK_EGRAD_LDS_STORE  // 1: a batch's results staged in LDS and stored as one coalesced
+#define MAXK_EGRAD_LDS_STORE 1  // run; 0: lane 0 of each group stores its own
+#endif
+
+namespace maxk {
+namespace {
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_f(float x) {
+    return __int_as_float(
+        __builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
+}
+
+// Sum over each aligned group of KG lanes, left in every lane of the group.  A butterfly of
+// fixed shape: both lanes of a pair add the same two numbers, so the group agrees bitwise.
+template <int KG>
+__device__ __forceinline__ float group_sum(float x) {
+    x += dpp_f<0xB1>(x);   // quad_perm [1,0,3,2]: lane ^ 1
+    x += dpp_f<0x4E>(x);   // quad_perm [2,3,0,1]: lane ^ 2
+    x += dpp_f<0x141>(x);  // row_half_mirror: the other quad of the 8 (all its lanes equal)
+    if constexpr (KG >= 16) x += dpp_f<0x140>(x);  // row_mirror: the other 8 of the 16
+    if constexpr (KG >= 32)  // ds_swizzle, bit mode, xor 0x10: the other 16 of the 32
+        x += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), 0x401F));
+    if constexpr (KG >= 64) {  // halves exchanged: r[0] = the low half's x, r[1] = the high's
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x),
+                                                        false, false);
+        x = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+    return x;
+}
+
+// grow[0:D] = G[row, :] (grow's pad columns [D, DS) already hold zeros).  One wave.
+__device__ __forceinline__ void stage_row(float *grow, const float *__restrict__ g, int D, bool vec,
+                                          int lane) {
+    if (vec) {
+        for (int j = lane * 4; j < D; j += kWave * 4)
+            *reinterpret_cast<float4 *>(&grow[j]) = *reinterpret_cast<const float4 *>(&g[j]);
+    } else {
+        for (int j = lane; j < D; j += kWave) grow[j] = g[j];
+    }
+}
+
+// grad_edge[e] = dot(record of col_idx[e], grow) / div over e in [sb, se), sb < se: a piece of
+// one row whose G row is staged in grow.  WIDE (tables past 2^24 columns or 4 GiB): 64-bit
+// record addresses and clamped loads instead of the buffer descriptors.
+template <int KG, int U, bool WIDE>
+__device__ __forceinline__ void walk_piece(const float *grow, float *stage,
+                                           const int32_t *__restrict__ col_idx,
+                                           const uint8_t *__restrict__ rec, int RS,
+                                           float *__restrict__ grad_edge, int sb, int se, int k,
+                                           int trash, float div, bool scale, int lane) {
+    constexpr int G = kWave / KG;
+    const int grp = lane / KG, l0 = lane % KG;
+    const int n = se - sb;  // wave-uniform, <= chunk
+    const auto crs = wave_buffer(col_idx + sb, (uint32_t)n * 4u);
+    const auto ors = wave_buffer(grad_edge + sb, (uint32_t)n * 4u);
+    const auto rrs = wave_buffer(rec, WIDE ? 0u : 0xffffffffu);
+    for (int base = 0; base < n; base += G * U) {
+        int c[U];
+        float acc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            c[u] = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, (base + u * G + grp) * 4, 0, 0);
+            acc[u] = 0.f;
+        }
+        for (int lb = 0; lb < k; lb += KG) {  // one pass unless k > 64
+            const int l = lb + l0;
+            const bool lok = l < k;
+            const uint32_t lc = (uint32_t)(lok ? l : k - 1);
+            float v[U];
+            int s[U];
+            if constexpr (!WIDE) {
+                const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+#pragma unroll
+                for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const uint8_t *p = rec + (size_t)(uint32_t)c[u] * RS;
+                    v[u] = reinterpret_cast<const float *>(p)[lc];
+                    s[u] = reinterpret_cast<const uint16_t *>(p + 4 * k)[lc];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float t = __builtin_fmaf(v[u], grow[min(s[u], trash)], acc[u]);
+                acc[u] = lok ? t : acc[u];  // an idle lane's clamped slot contributes nothing
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float x = group_sum<KG>(acc[u]);
+            acc[u] = scale ? x / div : x;
+        }
+        if constexpr (MAXK_EGRAD_LDS_STORE) {
+            // the batch's G * U results in edge order, one coalesced store of the run
+            wave_lds_fence();
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (l0 == 0) stage[u * G + grp] = acc[u];
+            wave_lds_fence();
+            const int e = base + lane;
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(stage[lane % (G * U)]), ors,
+                                                  lane < G * U ? e * 4 : (int)0x80000000, 0, 0);
+        } else {
+            // lane 0 of each group: G consecutive floats per instruction; past the piece's end
+            // (and from the other lanes) the offset is out of the descriptor's range: dropped
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                __builtin_amdgcn_raw_buffer_store_b32(
+                    __float_as_uint(acc[u]), ors,
+                    l0 == 0 ? (base + u * G + grp) * 4 : (int)0x80000000, 0, 0);
+        }
+    }
+}
+
+template <int KG, int U, bool WIDE>
+__global__ __launch_bounds__(kBlock) void edge_grad_kernel(
+    const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
+    const uint8_t *__restrict__ rec, int RS, const float *__restrict__ grad_out,
+    const float *__restrict__ row_div, float *__restrict__ grad_edge, int num_rows, int64_t num_e,
+    int D, int DS, int k, int chunk, int n_items, int vec) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int kStage = MAXK_EGRAD_LDS_STORE ? kWave : 0;
+    const int wid = threadIdx.x / kWave;
+    const int lane = lane_id();
+    const int blk = MAXK_FWD_XCD ? xcd_contiguous_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int item = blk * kWavesPerBlock + wid;
+    if (item >= n_items) return;  // whole wave; no workgroup barrier below
+    float *grow = lds + (size_t)wid * (DS + kStage);
+    float *stage = grow + DS;
+    // the pad columns [D, DS) are never staged over: zeroed once (DS - D <= 7)
+    if (lane < DS - D) grow[D + lane] = 0.f;
+
+    const int64_t total = (int64_t)num_rows + num_e;
+    const int64_t d0 = (int64_t)item * chunk;
+    const int64_t d1 = d0 + chunk < total ? d0 + chunk : total;
+    int r = wave_first_row_token(row_ptr, num_rows, d0);
+
+    // Row q's token is q + row_ptr[q], its edge e's e + q + 1.  The item walks the edges whose
+    // tokens lie in [d0, d1): first the tail of row r - 1 (its row token precedes d0), then the
+    // rows whose token it holds, the last one cut at d1.
+    int q = r - 1;
+    int64_t sb = d0 - r, se = 0;
+    if (r > 0) {
+        se = (int64_t)row_ptr[r];
+        if (d1 - r < se) se = d1 - r;
+    }
+    for (;;) {
+        if (q >= 0 && sb < se) {
+            const float div = row_div ? row_div[q] : 1.f;  // loaded before the walk
+            wave_lds_fence();  // the previous piece's reads of grow are done
+            stage_row(grow, grad_out + (int64_t)q * D, D, vec != 0, lane);
+            wave_lds_fence();
+            walk_piece<KG, U, WIDE>(grow, stage, col_idx, rec, RS, grad_edge, (int)sb, (int)se, k,
+                                    DS - 1, div, row_div != nullptr, lane);
+        }
+        ++q;
+        if (q >= num_rows) break;
+        sb = (int64_t)row_ptr[q];
+        if (sb + q >= d1) break;  // row q's token belongs to a later item
+        se = (int64_t)row_ptr[q + 1];
+        if (d1 - q - 1 < se) se = d1 - q - 1;
+    }
+}
+
+// Waves one CU holds at once: 8 per SIMD by VGPRs (at most 64, the kernel-resource-usage
+// remarks); the LDS row per wave (about 1 KB) is far from the CU's 160 KB.
+constexpr int kEdgeGradResident = 32;
+// An item's pieces are addressed through descriptors of 4 * n bytes with 32-bit offsets.
+constexpr int kEdgeGradMaxChunk = 1 << 24;
+
+struct EdgeGradLayout {
+    int chunk, n_items, RS, DS, kg;
+    bool wide;
+    size_t total;
+};
+
+EdgeGradLayout edge_grad_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, int k,
+                                int chunk) {
+    EdgeGradLayout L{};
+    L.RS = record_stride(k, num_cols);
+    L.DS = copy_stride(D);
+    const int g = lanes_per_edge(k);
+    L.kg = g < 8 ? 8 : g;
+    L.wide = !(num_cols < (1 << 24) && (uint64_t)num_cols * (uint64_t)L.RS < (1ull << 32));
+    L.chunk = fwd_chunk(num_rows, num_e, chunk, kEdgeGradResident);
+    if (L.chunk > kEdgeGradMaxChunk) L.chunk = kEdgeGradMaxChunk;
+    const int64_t n = ceil_div(num_rows + num_e, L.chunk);
+    L.n_items = (int)(n > 0 ? n : 1);
+    L.total = al256((size_t)num_cols * L.RS);
+    return L;
+}
+
+}  // namespace
+}  // namespace maxk
+
+using namespace maxk;
+
+extern "C" size_t maxk_edge_weight_grad_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                       int64_t num_e, int32_t dim_origin,
+                                                       int32_t dim_k, int32_t chunk_edges) {
+    if (num_rows < 0 || num_cols < 0 || num_e < 0 || dim_origin <= 0 || dim_k <= 0) return 0;
+    const size_t n =
+        edge_grad_layout(num_rows, num_cols, num_e, dim_origin, dim_k, chunk_edges).total;
+    return n ? n : 256;  // never empty: one query serves any num_cols
+}
+
+extern "C" int maxk_edge_weight_grad(const int32_t *row_ptr, const int32_t *col_idx,
+                                     const float *cbsr_val, const uint8_t *cbsr_idx,
+                                     const float *grad_out, const float *row_div,
+                                     float *grad_edge, int64_t num_rows, int64_t num_cols,
+                                     int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                                     int32_t chunk_edges, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    clear_error();
+    MAXK_REQUIRE(num_rows >= 0 && num_rows < (1LL << 31), "num_rows out of range: %lld",
+                 (long long)num_rows);
+    MAXK_REQUIRE(num_cols >= 0 && num_cols < (1LL << 31), "num_cols out of range");
+    MAXK_REQUIRE(num_e >= 0 && num_e < (1LL << 31), "num_e out of range: %lld", (long long)num_e);
+    MAXK_REQUIRE(dim_origin >= 1 && dim_origin <= kMaxDim, "dim_origin must be in [1,256], got %d",
+                 dim_origin);
+    MAXK_REQUIRE(dim_k >= 1 && dim_k <= dim_origin, "dim_k must be in [1,dim_origin], got %d",
+                 dim_k);
+    MAXK_REQUIRE(chunk_edges >= 0, "chunk_edges must be >= 0");
+    MAXK_REQUIRE(num_cols * (int64_t)dim_k < (1LL << 31), "num_cols*k too large");
+    if (num_e == 0) return MAXK_OK;  // no edge, nothing to write
+    MAXK_REQUIRE(num_rows > 0 && num_cols > 0, "edges present but num_rows or num_cols == 0");
+    MAXK_REQUIRE(row_ptr && col_idx && cbsr_val && cbsr_idx && grad_out && grad_edge,
+                 "CSR / CBSR / grad_out / grad_edge pointers must not be NULL");
+    const EdgeGradLayout L =
+        edge_grad_layout(num_rows, num_cols, num_e, dim_origin, dim_k, chunk_edges);
+    MAXK_REQUIRE(workspace && workspace_bytes >= L.total,
+                 "workspace too small: need %zu bytes, got %zu", L.total, workspace_bytes);
+    MAXK_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-B aligned");
+    MAXK_REQUIRE(((uintptr_t)cbsr_val & 3) == 0 && ((uintptr_t)grad_out & 3) == 0 &&
+                     ((uintptr_t)grad_edge & 3) == 0,
+                 "float buffers must be 4-B aligned");
+
+    hipStream_t s = as_stream(stream);
+    const int D = dim_origin, k = dim_k;
+    uint8_t *rec = reinterpret_cast<uint8_t *>(workspace);
+    if (int rc = launch_cbsr_pack(cbsr_val, cbsr_idx, rec, num_cols, k, L.RS, D, L.DS - 1, s))
+        return rc;
+    constexpr int U = MAXK_EGRAD_U;
+    const size_t lds =
+        (size_t)kWavesPerBlock * (L.DS + (MAXK_EGRAD_LDS_STORE ? kWave : 0)) * sizeof(float);
+    const int64_t blocks = ceil_div(L.n_items, kWavesPerBlock);
+    const dim3 grid((unsigned)(MAXK_FWD_XCD ? xcd_grid(blocks) : blocks));
+    const int vec = D % 4 == 0 && ((uintptr_t)grad_out & 15) == 0;
+    const bool ok = with_const<8, 16, 32, 64>(L.kg, [&](auto kg_c) {
+        constexpr int KG = decltype(kg_c)::value;
+        if (L.wide)
+            hipLaunchKernelGGL((edge_grad_kernel<KG, U, true>), grid, dim3(kBlock), lds, s, row_ptr,
+                               col_idx, rec, L.RS, grad_out, row_div, grad_edge, (int)num_rows,
+                               num_e, D, L.DS, k, L.chunk, L.n_items, vec);
+        else
+            hipLaunchKernelGGL((edge_grad_kernel<KG, U, false>), grid, dim3(kBlock), lds, s,
+                               row_ptr, col_idx, rec, L.RS, grad_out, row_div, grad_edge,
+                               (int)num_rows, num_e, D, L.DS, k, L.chunk, L.n_items, vec);
+    });
+    if (!ok) return bad_lanes(L.kg);
+    MAXK_LAUNCHED("edge_grad_kernel");
+    return MAXK_OK;
+}

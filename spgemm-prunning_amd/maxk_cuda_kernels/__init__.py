@@ -45,7 +45,8 @@ __all__ = [
     # MI355X additions
     "topk_cbsr", "cbsr_scatter_dense", "topk_cbsr_dense", "topk_backward", "topk_error_rows",
     "build_warp4_metadata", "warp4_to_indptr",
-    "spgemm_forward", "sspmm_backward", "DenseSpMMPlan", "version", "device_count",
+    "spgemm_forward", "sspmm_backward", "edge_weight_grad", "graph_only_mode", "DenseSpMMPlan",
+    "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
 ]
@@ -286,6 +287,48 @@ def spgemm_forward(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Te
                + ("_sel" if tail else ""), "maxk_spgemm_forward_workspace_size", shape,
                (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(cbsr_val), _ptr(cbsr_idx),
                 _ptr(row_div), _ptr(out), *shape), tail)
+    return out
+
+
+def edge_weight_grad(indptr: torch.Tensor, indices: torch.Tensor, cbsr_val: torch.Tensor,
+                     cbsr_idx: torch.Tensor, grad_output: torch.Tensor,
+                     row_div: Optional[torch.Tensor] = None, chunk: int = 0,
+                     out: Optional[torch.Tensor] = None,
+                     validate: Optional[bool] = None) -> torch.Tensor:
+    """grad_edge[E] float32: the forward's gradient with respect to the edge weights,
+    grad_edge[e] = sum_l cbsr_val[c, l] * grad_output[r, cbsr_idx[c, l]] / row_div[r] for edge
+    e of row r into column c = indices[e] (maxk_edge_weight_grad): the adjoint of
+    spgemm_forward in `values`, which it does not read.  Any k <= D <= 256; bitwise
+    repeatable.  The same operand checks as spgemm_forward / sspmm_backward."""
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (cbsr_val, "input_data", torch.float32),
+                     (cbsr_idx, "sparse_selector", torch.uint8),
+                     (grad_output, "grad_output", torch.float32)):
+        _need(t, n, dt)
+    if cbsr_val.dim() != 2 or cbsr_idx.shape != cbsr_val.shape:
+        raise RuntimeError("input_data and sparse_selector must have the same [V, k] shape")
+    num_cols, k = cbsr_val.shape
+    num_rows = indptr.numel() - 1
+    if grad_output.dim() != 2 or grad_output.shape[0] != num_rows:
+        raise RuntimeError("grad_output must be [num_rows, dim_origin]")
+    D = grad_output.shape[1]
+    if row_div is not None:
+        _need(row_div, "row_div", torch.float32)
+        if row_div.numel() != num_rows:
+            raise RuntimeError("row_div must have num_rows entries")
+    _validate_call(validate, indptr, indices, num_cols, cbsr_idx, D)
+    E = indices.numel()
+    dev = grad_output.device
+    if out is None:
+        out = torch.empty(E, dtype=torch.float32, device=dev)
+    else:
+        _need(out, "out", torch.float32)
+        if tuple(out.shape) != (E,):
+            raise RuntimeError("out must be [num_e]")
+    shape = (num_rows, num_cols, E, D, k, chunk)
+    _launch_ws(dev, "maxk_edge_weight_grad", "maxk_edge_weight_grad_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(grad_output),
+                _ptr(row_div), _ptr(out), *shape))
     return out
 
 
@@ -656,6 +699,26 @@ _MODE_NEEDS = {
 }
 
 
+def graph_only_mode(k: int, num_e: int, num_cols: int) -> Optional[str]:
+    """The feature backward's mode for differentiable edge weights, or None when a mode is
+    forced (MAXK_BWD_MODE set to anything but "auto").  The pull, dense and hybrid plans embed
+    the edge weights (pull_plan, dense_plan and hybrid_plan are keyed on `values`), so a weight
+    tensor that changes every step -- a Parameter updated in place, or attention coefficients,
+    a fresh tensor per call -- would rebuild such a plan on every call (Reddit-sized: the plan
+    build costs several forwards, profiles/r07/edge_grad/).  The choice is therefore among the
+    modes whose plans depend on the graph alone: "bsort" where maxk_backward_mode_auto's rule
+    for it holds (k % 4 == 0, k <= BSORT_KMAX, a window of maxk_bsort_window(k) edges holding
+    >= 2 rows per destination bucket), else "csc"."""
+    if os.environ.get("MAXK_BWD_MODE", "auto") != "auto":
+        return None
+    L = _lib()
+    k = int(k)
+    if (k > 0 and k % 4 == 0 and k <= BSORT_KMAX and num_e > 0 and
+            int(L.maxk_bsort_window(k)) * (1 << int(L.maxk_bucket_shift(k))) >= 2 * num_cols):
+        return "bsort"
+    return "csc"
+
+
 def backward_plan(indices: torch.Tensor, num_cols: int, k: int, mode: Optional[str] = None,
                   num_rows: Optional[int] = None, indptr: Optional[torch.Tensor] = None,
                   values: Optional[torch.Tensor] = None, dim: Optional[int] = None):
@@ -696,7 +759,10 @@ def sspmm_backward(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Te
     instead of gathered.
 
     mode "auto" (default; MAXK_BWD_MODE overrides): "dense", "pull", "hybrid", "bsort" or
-    "csc", see _bwd_mode.
+    "csc", see _bwd_mode.  The autograd surface (maxk_spgemm_function) does not leave the choice
+    to "auto" when the edge weights require grad: it passes graph_only_mode()'s "bsort" or
+    "csc", whose plans depend on the graph alone, since the pull, dense and hybrid plans embed
+    the weights and would be rebuilt whenever they change.
     mode "pull": per tile (row slice, destination bucket), the k values of every edge
     gathered from G and summed in fp64 LDS accumulators, no contribution rows (with a
     row_div the plan's weights are pre-divided, once per divisor: _scaled_entries);
@@ -886,16 +952,18 @@ def edge_selectors_wanted(k: int) -> bool:
 
 
 def edge_selector_mode(indptr: torch.Tensor, indices: torch.Tensor, k: int, num_cols: int,
-                       dim: Optional[int] = None) -> Optional[str]:
+                       dim: Optional[int] = None, mode: Optional[str] = None) -> Optional[str]:
     """The backward mode a forward should write the per-edge selector stream for
     (spgemm_forward(edge_sel_out=) -> sspmm_backward(edge_sel=, mode=)), or None: the backward
     resolves to "csc" or "bsort" (large sparse graphs without locality, where phase 1
     otherwise gathers a 128-B line of the selector table per edge) and
-    edge_selectors_wanted(k).  The stream holds num_e * k bytes until the backward."""
+    edge_selectors_wanted(k).  The stream holds num_e * k bytes until the backward.  `mode`:
+    the backward's mode when the caller has already resolved it (graph_only_mode)."""
     if indices.numel() == 0 or not edge_selectors_wanted(k):
         return None
-    mode = _bwd_mode(None, k, indices.numel(), num_cols, indptr.numel() - 1, dim,
-                     (indptr, indices))
+    if mode is None:
+        mode = _bwd_mode(None, k, indices.numel(), num_cols, indptr.numel() - 1, dim,
+                         (indptr, indices))
     return mode if mode in ("csc", "bsort") else None
 
 

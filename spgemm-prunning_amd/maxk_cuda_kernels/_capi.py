@@ -44,6 +44,9 @@ SIGNATURES = {
     "maxk_cbsr_records": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _p]),
     "maxk_spgemm_forward_records": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32,
                                                    _i32, _i32, _p, _sz, _p, _i32]),
+    "maxk_edge_weight_grad_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
+    "maxk_edge_weight_grad": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
+                                             _i32, _i32, _i32, _p, _sz, _p]),
     "maxk_sspmm_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
     "maxk_sspmm_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                            _i32, _i32, _i32, _p, _sz, _p]),

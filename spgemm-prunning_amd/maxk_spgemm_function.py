@@ -32,6 +32,17 @@ Fixed caller-visible defects of the reference (DESIGN.md "Boundary"):
     rule on any graph: G / out_degrees when given, else G undivided;
   * graph_indices_T / graph_values_T are accepted and unused: the kernel forms
     the A^T product from the CSR itself.
+
+Edge weights that require grad (attention coefficients, learned gates, a learnable
+normalisation): both call shapes return d out / d graph_values, in graph_values' dtype and
+shape (maxk_cuda_kernels.edge_weight_grad; the reference returns None).  The forward then also
+saves the CBSR values and its own divisor -- nothing extra otherwise.  The weight gradient
+always divides by the forward's divisor: it is the exact adjoint, and
+`backward_divisor="reference"` changes only the feature gradient.  With such weights and no
+mode forced through MAXK_BWD_MODE, the feature backward is resolved among the modes whose plans
+depend on the graph alone ("bsort" where its rule holds, else "csc":
+maxk_cuda_kernels.graph_only_mode), because the pull, dense and hybrid plans embed the weights
+and would be rebuilt on every step.
 """
 from __future__ import annotations
 
@@ -129,14 +140,34 @@ def _f32_act(t):
     return t.float().contiguous()
 
 
-def _edge_sel_for(indptr, indices, k, num_cols, D):
+def _edge_sel_for(indptr, indices, k, num_cols, D, bwd_mode=None):
     """(buffer, mode): the [E, k] u8 buffer the forward writes each edge's selectors into
     when the backward will be a two-phase form reading them ("csc" or "bsort",
-    maxk_cuda_kernels.edge_selector_mode), else (None, None)."""
-    mode = maxk_cuda_kernels.edge_selector_mode(indptr, indices, k, num_cols, D)
+    maxk_cuda_kernels.edge_selector_mode), else (None, None).  bwd_mode: the backward's mode
+    where the forward has fixed it already (_weight_grad_mode)."""
+    mode = maxk_cuda_kernels.edge_selector_mode(indptr, indices, k, num_cols, D, bwd_mode)
     if mode is None:
         return None, None
     return torch.empty(indices.numel(), k, dtype=torch.uint8, device=indices.device), mode
+
+
+def _weight_grad_mode(ctx, indices, k, num_cols):
+    """ctx.wgrad: the edge weights (apply() argument 1) require grad; ctx.bwd_mode: then the
+    feature backward's mode among those whose plans depend on the graph alone
+    (maxk_cuda_kernels.graph_only_mode), None otherwise or when MAXK_BWD_MODE forces one."""
+    ctx.wgrad = bool(ctx.needs_input_grad[1])
+    ctx.bwd_mode = (maxk_cuda_kernels.graph_only_mode(k, indices.numel(), num_cols)
+                    if ctx.wgrad else None)
+    return ctx.bwd_mode
+
+
+def _save(ctx, base, cbsr_val, fwd_div):
+    """The backward's operands; with differentiable edge weights also the CBSR values and the
+    forward's own divisor (the weight gradient is the exact adjoint whatever divides G)."""
+    ctx.has_fwd_div = fwd_div is not None
+    if ctx.wgrad:
+        base = base + (cbsr_val, fwd_div if fwd_div is not None else torch.empty(0))
+    ctx.save_for_backward(*base)
 
 
 class MaxKSpGEMMFunction(Function):
@@ -177,14 +208,15 @@ class MaxKSpGEMMFunction(Function):
         # the backward's divisor of G's rows: the forward's own (the exact adjoint), or the
         # reference's rule, G / out_degrees when given and G undivided otherwise (:154-159)
         bwd_div = _f32(out_degrees) if backward_divisor == "reference" else row_div
-        es, ctx.es_mode = _edge_sel_for(indptr, graph_indices, k, V, D)
+        es, ctx.es_mode = _edge_sel_for(indptr, graph_indices, k, V, D,
+                                        _weight_grad_mode(ctx, graph_indices, k, V))
         out = maxk_cuda_kernels.spgemm_forward(indptr, graph_indices, _f32(graph_values),
                                                sparse_data, sparse_selector, D, row_div=row_div,
                                                edge_sel_out=es)
         ctx.shape_v1 = (V, D)
-        ctx.save_for_backward(indptr, graph_indices, graph_values, sparse_selector,
-                              bwd_div if bwd_div is not None else torch.empty(0),
-                              es if es is not None else torch.empty(0))
+        _save(ctx, (indptr, graph_indices, graph_values, sparse_selector,
+                    bwd_div if bwd_div is not None else torch.empty(0),
+                    es if es is not None else torch.empty(0)), sparse_data, row_div)
         ctx.has_div = bwd_div is not None
         ctx.has_es = es is not None
         ctx.mode = "v1"
@@ -202,12 +234,13 @@ class MaxKSpGEMMFunction(Function):
         D = int(dim_origin) if dim_origin is not None else FULL_DIM
         indptr = _indptr_for(graph_indptr, warp4_metadata, num_warps, V)
         row_div = _f32(degrees)
-        es, ctx.es_mode = _edge_sel_for(indptr, graph_indices, k, V, D)
+        es, ctx.es_mode = _edge_sel_for(indptr, graph_indices, k, V, D,
+                                        _weight_grad_mode(ctx, graph_indices, k, V))
         out = maxk_cuda_kernels.spgemm_forward(indptr, graph_indices, _f32(graph_values), vals,
                                                sel, D, row_div=row_div, edge_sel_out=es)
-        ctx.save_for_backward(indptr, graph_indices, graph_values, sel,
-                              row_div if row_div is not None else torch.empty(0),
-                              es if es is not None else torch.empty(0))
+        _save(ctx, (indptr, graph_indices, graph_values, sel,
+                    row_div if row_div is not None else torch.empty(0),
+                    es if es is not None else torch.empty(0)), vals, row_div)
         ctx.has_div = row_div is not None
         ctx.has_es = es is not None
         ctx.mode = "v4"
@@ -215,17 +248,25 @@ class MaxKSpGEMMFunction(Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        indptr, graph_indices, graph_values, sel, row_div, es = ctx.saved_tensors
+        indptr, graph_indices, graph_values, sel, row_div, es = ctx.saved_tensors[:6]
         row_div = row_div if ctx.has_div else None
         g = grad_output.contiguous()
         if g.dtype != torch.float32:
             g = g.float()
         # with the forward's edge-selector stream the backward is the two-phase form (csc or
-        # bsort) the forward resolved, reading it
+        # bsort) the forward resolved, reading it; with differentiable edge weights, the
+        # graph-only mode the forward resolved
         grad_sparse = maxk_cuda_kernels.sspmm_backward(
             indptr, graph_indices, _f32(graph_values), g, sel, row_div=row_div,
-            edge_sel=es if ctx.has_es else None, mode=ctx.es_mode if ctx.has_es else None)
+            edge_sel=es if ctx.has_es else None,
+            mode=ctx.es_mode if ctx.has_es else ctx.bwd_mode)
         grads = [None] * ctx.n_inputs
+        if ctx.wgrad:
+            cbsr_val, fwd_div = ctx.saved_tensors[6:8]
+            grad_edge = maxk_cuda_kernels.edge_weight_grad(
+                indptr, graph_indices, cbsr_val, sel, g,
+                row_div=fwd_div if ctx.has_fwd_div else None)
+            grads[1] = grad_edge.to(graph_values.dtype).reshape(graph_values.shape)
         if ctx.mode == "v1":
             V, D = ctx.shape_v1
             if ctx.needs_input_grad[2]:
