@@ -10,10 +10,12 @@
 #include <type_traits>
 
 #include "maxk_hip.h"
+#include "token_items.h"  // the token-stream work partition: items, cut rules, row hand-out
 
 namespace maxk {
 
 constexpr int kWave = 64;          // CDNA wavefront
+static_assert(kPtrWindow == kWave, "a pointer window holds one entry per lane");
 constexpr int kBlock = 256;        // threads per workgroup (4 waves; 512 / 1024 measured slower)
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxDim = 256;       // uint8 selector range: per-wave LDS rows are 256 floats
@@ -375,37 +377,6 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
-// Token-stream work partition shared by the SpGEMM/SSpMM kernels: row r's token
-// sits at r + row_ptr[r], edge e of row q at e + q + 1; a work item owns a
-// contiguous token range.  Returns the first r in [0, n] whose token is >= d
-// (row_ptr[n] + n >= d required).  64-ary search by the whole wave; the result
-// is wave-uniform.
-__device__ __forceinline__ int wave_first_row_token(const int32_t *__restrict__ row_ptr, int n,
-                                                    int64_t d) {
-    const int lane = lane_id();
-    int lo = 0, hi = n;  // answer in [lo, hi]
-    while (hi - lo > 63) {
-        const int step = (hi - lo + 62) / 63;  // lo + 63*step >= hi
-        int p = lo + lane * step;
-        p = p > hi ? hi : p;
-        const uint64_t m = __ballot((int64_t)row_ptr[p] + p >= d);  // lane 63 probes hi: true
-        const int f = __builtin_ctzll(m);
-        if (f == 0) {
-            hi = lo;
-        } else {
-            const int pf = lo + f * step;
-            lo = lo + (f - 1) * step + 1;
-            hi = pf > hi ? hi : pf;
-        }
-    }
-    const int p = lo + lane;
-    const int pc = p > hi ? hi : p;
-    const uint64_t m = __ballot(p <= hi && (int64_t)row_ptr[pc] + pc >= d) | (1ull << 63);
-    const int r = lo + __builtin_ctzll(m);
-    return r > hi ? hi : r;
-}
-
 
 // ---- split-row fixup shared by the forward (TAG 0) and the backward's phase 2 (TAG 1) ----
 // out[row, 0:width] += slab[i, 0:width] for every run of consecutive items i whose

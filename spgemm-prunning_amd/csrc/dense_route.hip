@@ -11,9 +11,11 @@
 //             columns, grad_cbsr[c, l] = Y[c, sel[c, l]] (selectors >= D read 0, as in every
 //             mode); rows split over items are finished by dense_fixup_select_kernel.
 //
-// dense_rows_kernel reads the CSR as the token stream of common.h (one wave per item of
-// `chunk` tokens).  The item's column ids and weights (divided by src_div when given) are staged
-// in LDS with coalesced loads.  Lane groups of LR = pow2ceil(D / 4) lanes (a float4 each) take
+// dense_rows_kernel reads the CSR as the token stream of token_items.h (one wave per item of
+// `chunk` tokens, its hub-row cut rule CutHubRows; pick_rows_kernel's rows are handed to the
+// lane groups by its RowHandout, dense_rows_body keeps that hand-out written out).  The item's
+// column ids and weights (divided by src_div when given) are staged in LDS with coalesced loads.
+// Lane groups of LR = pow2ceil(D / 4) lanes (a float4 each) take
 // whole rows of at most kDenseGroupMax of the item's edges: a group walks its row U edges per
 // step into registers, stores it the step it ends and takes the item's next row, so 64 / LR rows
 // are in flight per wave and the next step's gathers are issued before this step's sums.  A
@@ -99,6 +101,24 @@ __global__ __launch_bounds__(kDenseBlock) void cbsr_dense_kernel(const float *__
     }
 }
 
+// The ids and weights (divided by src_div when given) of the item's edges, from p_lo on: up to
+// 2 * chunk of them (CutHubRows), copied to the wave's LDS stage with coalesced loads.
+__device__ __forceinline__ void stage_edges(int32_t *s_idx, float *s_sc,
+                                            const int32_t *__restrict__ idx,
+                                            const float *__restrict__ w,
+                                            const float *__restrict__ src_div, int64_t p_lo,
+                                            int64_t num_e, int chunk, int lane) {
+    const int64_t span = 2 * (int64_t)chunk;
+    const int n_pos = (int)(num_e - p_lo < span ? num_e - p_lo : span);
+    for (int i = lane; i < n_pos; i += kWave) {
+        const int c = idx[p_lo + i];
+        const float wv = w[p_lo + i];
+        s_idx[i] = c;
+        s_sc[i] = src_div ? wv / src_div[c] : wv;
+    }
+    wave_lds_fence();
+}
+
 __device__ __forceinline__ void fma4(float4 &a, float s, const float4 &v) {
     a.x = __builtin_fmaf(s, v.x, a.x);
     a.y = __builtin_fmaf(s, v.y, a.y);
@@ -126,9 +146,8 @@ __device__ __forceinline__ void store_row4(float *dst, float4 a, bool has_div, f
     *p = a;
 }
 
-// Rows are owned by the item holding their token.  A row of at most `chunk` edges is walked
-// whole by its owner, past the item's end if it must (so an item walks at most 2 * chunk
-// tokens; the LDS stage holds that many edges); only a longer (hub) row is split at item ends:
+// Rows are cut by CutHubRows (token_items.h): an item walks at most 2 * chunk tokens, and the
+// LDS stage holds that many edges.  A hub row split at item ends:
 // its owner stores a partial, every later item it reaches stores a partial to its slab, and
 // slab_fixup_kernel (forward) / dense_fixup_select_kernel (backward) add the slabs in item
 // order.  (Finishing hub rows inside the walk -- the last item to reach one adding the slabs,
@@ -156,11 +175,9 @@ __device__ __forceinline__ void dense_rows_body(
     const int D4 = D >> 2;
     const bool qok = q < D4;
     const float4 *__restrict__ X4 = reinterpret_cast<const float4 *>(X);
-    const int64_t total = (int64_t)num_rows + num_e;
-    const int64_t d0 = (int64_t)item * chunk;
-    const int64_t d1 = d0 + chunk < total ? d0 + chunk : total;
-    int r = wave_first_row_token(ptr, num_rows, d0);
-    const int64_t p_lo = d0 - r;  // the item's first edge (the tokens before d0 hold r rows)
+    const ItemRange it = item_range(ptr, num_rows, num_e, item, chunk);
+    const int64_t d1 = it.d1, p_lo = it.p_lo;
+    int r = it.r;
     int32_t *s_idx = s_stage + (size_t)wid * (4 * chunk + (SEL ? 4 * kWave : 0));
     float *s_sc = reinterpret_cast<float *>(s_idx + 2 * chunk);
     float *s_buf = s_sc + 2 * chunk;  // SEL: group g's row copy at g * 4 * LR
@@ -183,17 +200,7 @@ __device__ __forceinline__ void dense_rows_body(
         }
         wave_lds_fence();  // the copy is reused by the group's next row
     };
-    {
-        const int64_t span = 2 * (int64_t)chunk;
-        const int n_pos = (int)(num_e - p_lo < span ? num_e - p_lo : span);
-        for (int i = lane; i < n_pos; i += kWave) {
-            const int c = idx[p_lo + i];
-            const float wv = w[p_lo + i];
-            s_idx[i] = c;
-            s_sc[i] = src_div ? wv / src_div[c] : wv;
-        }
-        wave_lds_fence();
-    }
+    stage_edges(s_idx, s_sc, idx, w, src_div, p_lo, num_e, chunk, lane);
     // edges [sb, se) of one row by the whole wave: edge sb + j to group j % NG
     auto wave_row = [&](int64_t sb, int64_t se) -> float4 {
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -226,13 +233,10 @@ __device__ __forceinline__ void dense_rows_body(
     // continuation of hub row r - 1 (its token precedes d0): this item's part goes to its slab
     int cont = -1;
     if (r > 0) {
-        const int64_t rp = ptr[r - 1];
-        int64_t se = (int64_t)ptr[r];
-        const bool hub = se - rp > chunk;
-        if (d1 - r < se) se = d1 - r;
-        if (hub && p_lo < se) {
+        const RowPiece p = cont_piece(CutHubRows{}, it.p_lo, d1, r, ptr[r - 1], ptr[r], chunk);
+        if (p.hub && p.sb < p.se) {
             const float div = dst_div ? dst_div[r - 1] : 1.f;
-            const float4 a = wave_row(p_lo, se);
+            const float4 a = wave_row(p.sb, p.se);
             if (g == 0 && qok)
                 store_row4(slab + (int64_t)item * D + 4 * q, a, dst_div != nullptr, div, false);
             cont = r - 1;
@@ -244,6 +248,9 @@ __device__ __forceinline__ void dense_rows_body(
     while (r < num_rows) {
         // whole rows of at most lmax edges by the lane groups
         {
+            // The same hand-out as RowHandout<CutHubRows> (token_items.h), written out here:
+            // through the shared form this walk's forward is 6 % slower on the Flickr-sized graph
+            // at equal register figures (profiles/r09/token_items/ab.md).
             int wb = r;  // ptr window: rows [wb, wb + 64), one per lane
             int rpw = ptr[wb + lane <= num_rows ? wb + lane : num_rows];
             int next = r;       // the next row to hand out (wave-uniform)
@@ -261,7 +268,7 @@ __device__ __forceinline__ void dense_rows_body(
                     }
                     const int64_t rb = __builtin_amdgcn_readlane(rpw, next - wb);
                     const int64_t re = __builtin_amdgcn_readlane(rpw, next + 1 - wb);
-                    if (next < num_rows && next + rb < d1 && re - rb <= lmax) {
+                    if (next < num_rows && row_owned(d1, next, rb) && re - rb <= lmax) {
                         if (g == gi) {
                             row = next;
                             t = rb;
@@ -323,11 +330,11 @@ __device__ __forceinline__ void dense_rows_body(
         }
         if (r >= num_rows) break;
         const int64_t rb = ptr[r];
-        if (rb + r >= d1) break;
+        if (!row_owned(d1, r, rb)) break;
         // a longer row by the whole wave: whole up to chunk edges, else a hub row split at d1
-        const int64_t re = (int64_t)ptr[r + 1];
-        const bool hub = re - rb > chunk;
-        const int64_t se = hub && d1 - r - 1 < re ? d1 - r - 1 : re;
+        const RowPiece p = row_piece(CutHubRows{}, d1, r, rb, ptr[r + 1], chunk);
+        const bool hub = p.hub;
+        const int64_t se = p.se;
         const float div = dst_div ? dst_div[r] : 1.f;
         const uint32_t selw = SEL && q < kw ? sel32[(int64_t)r * kw + q] : 0u;
         const float4 a = wave_row(rb, se);
@@ -384,24 +391,12 @@ __global__ __launch_bounds__(kBlock, U <= 4 ? 6 : 4) void pick_rows_kernel(
     if (item >= n_items) return;  // whole wave; no workgroup barrier below
     const int g = lane / LR, q = lane % LR;
     const bool qok = q < k;
-    const int64_t total = (int64_t)num_rows + num_e;
-    const int64_t d0 = (int64_t)item * chunk;
-    const int64_t d1 = d0 + chunk < total ? d0 + chunk : total;
-    int r = wave_first_row_token(ptr, num_rows, d0);
-    const int64_t p_lo = d0 - r;
+    const ItemRange it = item_range(ptr, num_rows, num_e, item, chunk);
+    const int64_t d1 = it.d1, p_lo = it.p_lo;
+    int r = it.r;
     int32_t *s_idx = s_stage + (size_t)wid * 4 * chunk;
     float *s_sc = reinterpret_cast<float *>(s_idx + 2 * chunk);
-    {
-        const int64_t span = 2 * (int64_t)chunk;
-        const int n_pos = (int)(num_e - p_lo < span ? num_e - p_lo : span);
-        for (int i = lane; i < n_pos; i += kWave) {
-            const int c = idx[p_lo + i];
-            const float wv = w[p_lo + i];
-            s_idx[i] = c;
-            s_sc[i] = src_div ? wv / src_div[c] : wv;
-        }
-        wave_lds_fence();
-    }
+    stage_edges(s_idx, s_sc, idx, w, src_div, p_lo, num_e, chunk, lane);
     // this lane's column of row c (D: reads 0)
     auto col_of = [&](int c) -> int {
         const int sv = qok ? (int)sel[(int64_t)c * k + q] : D;
@@ -434,12 +429,9 @@ __global__ __launch_bounds__(kBlock, U <= 4 ? 6 : 4) void pick_rows_kernel(
 
     int cont = -1;
     if (r > 0) {
-        const int64_t rp = ptr[r - 1];
-        int64_t se = (int64_t)ptr[r];
-        const bool hub = se - rp > chunk;
-        if (d1 - r < se) se = d1 - r;
-        if (hub && p_lo < se) {
-            const float a = wave_row(p_lo, se, col_of(r - 1));
+        const RowPiece p = cont_piece(CutHubRows{}, it.p_lo, d1, r, ptr[r - 1], ptr[r], chunk);
+        if (p.hub && p.sb < p.se) {
+            const float a = wave_row(p.sb, p.se, col_of(r - 1));
             if (g == 0 && qok) slab[(int64_t)item * k + q] = a;
             cont = r - 1;
         }
@@ -449,34 +441,16 @@ __global__ __launch_bounds__(kBlock, U <= 4 ? 6 : 4) void pick_rows_kernel(
     const int lmax = chunk < kDenseGroupMax ? chunk : kDenseGroupMax;
     while (r < num_rows) {
         {
-            int wb = r;
-            int rpw = ptr[wb + lane <= num_rows ? wb + lane : num_rows];
-            int next = r;
-            bool stop = false;
+            RowHandout<CutHubRows> h(ptr, num_rows, r, d1, lmax, lane);
             int row = -1, col = D;
             int64_t t = 0, te = 0;
             auto assign = [&]() {
-                const uint64_t idle = __ballot(row < 0);
-                for (int gi = 0; gi < NG && !stop; ++gi) {
-                    if (!((idle >> (gi * LR)) & 1ull)) continue;
-                    if (next + 1 >= wb + kWave) {
-                        wb = next;
-                        rpw = ptr[wb + lane <= num_rows ? wb + lane : num_rows];
-                    }
-                    const int64_t rb = __builtin_amdgcn_readlane(rpw, next - wb);
-                    const int64_t re = __builtin_amdgcn_readlane(rpw, next + 1 - wb);
-                    if (next < num_rows && next + rb < d1 && re - rb <= lmax) {
-                        if (g == gi) {
-                            row = next;
-                            t = rb;
-                            te = re;
-                            col = col_of(next);
-                        }
-                        ++next;
-                    } else {
-                        stop = true;
-                    }
-                }
+                h.assign<(NG <= 8 ? NG : 1)>(row < 0, NG, LR, g, lane, [&](int q_, int rb, int re) {
+                    row = q_;
+                    t = rb;
+                    te = re;
+                    col = col_of(q_);
+                });
             };
             auto gather = [&](float (&v)[U], float (&sc)[U]) {
 #pragma unroll
@@ -513,14 +487,12 @@ __global__ __launch_bounds__(kBlock, U <= 4 ? 6 : 4) void pick_rows_kernel(
                     a = 0.f;
                 }
             }
-            r = next;
+            r = h.next;
         }
         if (r >= num_rows) break;
         const int64_t rb = ptr[r];
-        if (rb + r >= d1) break;
-        const int64_t re = (int64_t)ptr[r + 1];
-        const bool hub = re - rb > chunk;
-        const int64_t se = hub && d1 - r - 1 < re ? d1 - r - 1 : re;
+        if (!row_owned(d1, r, rb)) break;
+        const int64_t se = row_piece(CutHubRows{}, d1, r, rb, ptr[r + 1], chunk).se;
         const float a = wave_row(rb, se, col_of(r));
         if (g == 0 && qok) grad_cbsr[(int64_t)r * k + q] = a;  // a hub row's owner: its partial
         ++r;
@@ -666,8 +638,7 @@ DenseLayout dense_layout(int64_t rows, int64_t x_rows, int64_t num_e, int D, int
     DenseLayout L{};
     L.chunk = dense_chunk(rows + num_e, chunk,
                           dense_slots(kind == 2 ? lanes_per_edge(width) : dense_lanes(D), kind));
-    const int64_t n = ceil_div(rows + num_e, L.chunk);
-    L.n_items = (int)(n > 0 ? n : 1);
+    L.n_items = token_items(rows, num_e, L.chunk);
     L.x_off = 0;
     L.slab_off = al256((size_t)x_rows * D * sizeof(float));
     L.row_off = L.slab_off + al256((size_t)L.n_items * width * sizeof(float));

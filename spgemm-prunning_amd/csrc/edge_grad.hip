@@ -6,15 +6,15 @@
 //
 // the adjoint of out = diag(1/row_div) . A . scatter(cbsr) in A's values.  It shares the
 // forward's gather -- one packed record [k f32 | k u16 | pad] per edge (cbsr_pack.h), so an edge
-// costs one line -- and its token-stream partition (common.h), and nothing else:
+// costs one line -- and its token-stream partition (token_items.h), and nothing else:
 //
 //  1. launch_cbsr_pack writes this call's records into the workspace.  The pack folds repeated
 //     selectors into their first occurrence and sends selectors >= D to the trash column with
 //     value 0, so every term of an edge's dot product is either a kept (value, column < D) pair
 //     or exactly 0 * 0.
-//  2. edge_grad_kernel, one wavefront per item of `chunk` tokens.  An item walks exactly the
-//     edges whose tokens it holds: every edge's result is independent, so a hub row cut over
-//     items needs no slab and no fix-up -- each item stages the row again.
+//  2. edge_grad_kernel, one wavefront per item of `chunk` tokens, cut at the item's end
+//     (CutAtEnd): every edge's result is independent, so a hub row cut over items needs no
+//     slab and no fix-up -- each item stages the row again.
 //     * per row piece: G[r, :] staged once into the wave's LDS row (16-B loads where D % 4 == 0
 //       and grad_out is 16-B aligned, else scalar); the pad columns [D, DS) hold zeros, so a
 //       skipped selector reads 0 even beside a NaN in G;
@@ -172,21 +172,16 @@ __global__ __launch_bounds__(kBlock) void edge_grad_kernel(
     // the pad columns [D, DS) are never staged over: zeroed once (DS - D <= 7)
     if (lane < DS - D) grow[D + lane] = 0.f;
 
-    const int64_t total = (int64_t)num_rows + num_e;
-    const int64_t d0 = (int64_t)item * chunk;
-    const int64_t d1 = d0 + chunk < total ? d0 + chunk : total;
-    int r = wave_first_row_token(row_ptr, num_rows, d0);
+    const ItemRange it = item_range(row_ptr, num_rows, num_e, item, chunk);
 
-    // Row q's token is q + row_ptr[q], its edge e's e + q + 1.  The item walks the edges whose
-    // tokens lie in [d0, d1): first the tail of row r - 1 (its row token precedes d0), then the
-    // rows whose token it holds, the last one cut at d1.
-    int q = r - 1;
-    int64_t sb = d0 - r, se = 0;
-    if (r > 0) {
-        se = (int64_t)row_ptr[r];
-        if (d1 - r < se) se = d1 - r;
-    }
+    // The item walks the edges whose tokens lie in [d0, d1) (CutAtEnd): first the tail of row
+    // r - 1 (its row token precedes d0), then the rows whose token it holds, the last one cut
+    // at d1.
+    int q = it.r - 1;
+    RowPiece p{0, 0, false};
+    if (it.r > 0) p = cont_piece(CutAtEnd{}, it.p_lo, it.d1, it.r, row_ptr[it.r]);
     for (;;) {
+        const int64_t sb = p.sb, se = p.se;
         if (q >= 0 && sb < se) {
             const float div = row_div ? row_div[q] : 1.f;  // loaded before the walk
             wave_lds_fence();  // the previous piece's reads of grow are done
@@ -197,10 +192,9 @@ __global__ __launch_bounds__(kBlock) void edge_grad_kernel(
         }
         ++q;
         if (q >= num_rows) break;
-        sb = (int64_t)row_ptr[q];
-        if (sb + q >= d1) break;  // row q's token belongs to a later item
-        se = (int64_t)row_ptr[q + 1];
-        if (d1 - q - 1 < se) se = d1 - q - 1;
+        const int64_t rb = row_ptr[q];
+        if (!row_owned(it.d1, q, rb)) break;  // row q's token belongs to a later item
+        p = row_piece(CutAtEnd{}, it.d1, q, rb, row_ptr[q + 1]);
     }
 }
 
@@ -226,8 +220,7 @@ EdgeGradLayout edge_grad_layout(int64_t num_rows, int64_t num_cols, int64_t num_
     L.wide = !(num_cols < (1 << 24) && (uint64_t)num_cols * (uint64_t)L.RS < (1ull << 32));
     L.chunk = fwd_chunk(num_rows, num_e, chunk, kEdgeGradResident);
     if (L.chunk > kEdgeGradMaxChunk) L.chunk = kEdgeGradMaxChunk;
-    const int64_t n = ceil_div(num_rows + num_e, L.chunk);
-    L.n_items = (int)(n > 0 ? n : 1);
+    L.n_items = token_items(num_rows, num_e, L.chunk);
     L.total = al256((size_t)num_cols * L.RS);
     return L;
 }

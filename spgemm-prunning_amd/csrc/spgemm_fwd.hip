@@ -12,9 +12,8 @@
 //     input.  Measured on MI355X (tools/fwd_probe.hip): 1 line/edge instead of 2
 //     takes the Reddit-sized forward from 2.8 ms to 1.9 ms.
 //  2. spgemm_fwd_kernel, one wavefront per work item:
-//     * work partition: the CSR is read as a token stream of V row tokens and E
-//       edge tokens (common.h); item i = tokens [i*C, (i+1)*C) -> every wave gets
-//       <= C edges and <= C rows whatever the degree skew;
+//     * work partition: the token stream of token_items.h under its hub-row cut rule
+//       (CutHubRows) -> every wave gets < 2C edges and <= C rows whatever the degree skew;
 //     * KG = pow2ceil(k) (>= 8) lanes per edge, G = 64/KG edges per wave step,
 //       U steps in flight, all loads unconditional (clamped addresses);
 //     * accumulation: G LDS copies of the output row, one per edge group, with
@@ -455,10 +454,9 @@ __device__ __forceinline__ void store_out4(float *dst, float4 a, bool scale, flo
 // loaded while this step's records are in flight.  A row then costs about one dependent round
 // of loads per U edges, against two in the batched path (columns, then records), which on a
 // small sparse graph -- one round of waves, each a chain of such rounds -- is the whole time.
-// A group flushes its finished row from its own LDS copy (16-B stores).  Rows are taken in
-// order while the next one is owned by the item (token < d1) and has at most lmax edges (the
-// callers pass at most `chunk`: a longer row is split over items, and its pieces past d1 belong
-// to the items holding them);
+// A group flushes its finished row from its own LDS copy (16-B stores).  Rows are handed out by
+// RowHandout<CutHubRows> (token_items.h): in order while the next one is owned by the item and
+// has at most lmax edges (the callers pass at most `chunk`, so the groups take whole rows only);
 // returns the first row not taken (the caller walks a longer one with the whole wave).  Copies
 // are zero on entry and on return.  D % 4 == 0.
 template <int KG, int U, class Src>
@@ -474,40 +472,20 @@ __device__ __forceinline__ int stream_rows(float *acc, int DS, int r,
     float *acc_g = acc + g * DS;
     const bool lok = l0 < k;
     const bool add = flags & 1, nt = flags & 2;
-    // row_ptr window: rows [wb, wb + 64), one per lane
-    int wb = r;
-    int rpw = row_ptr[wb + lane <= num_rows ? wb + lane : num_rows];
-    const int ebase = __builtin_amdgcn_readfirstlane(rpw);  // = row_ptr[r]
+    RowHandout<CutHubRows> h(row_ptr, num_rows, r, d1, lmax, lane);
+    const int ebase = __builtin_amdgcn_readfirstlane(h.win.v);  // = row_ptr[r]
     const int64_t span = (num_e - ebase) * 4;
     const auto crs = wave_buffer(col_idx + ebase, (uint32_t)(span < 0xffffffffLL ? span : 0xffffffffLL));
     const auto vrs = wave_buffer(edge_val + ebase, (uint32_t)(span < 0xffffffffLL ? span : 0xffffffffLL));
-    int next = r;       // the next row to hand out (wave-uniform)
-    bool stop = false;  // the next row is not the item's or is too long (wave-uniform)
     int row = -1, e = 0, ee = 0;  // this group's row and its edge range [e, ee)
     float div = 1.f;
     auto assign = [&]() {
-        const uint64_t idle = __ballot(row < 0);
-#pragma unroll
-        for (int gi = 0; gi < NC; ++gi) {
-            if (stop || !((idle >> (gi * KG)) & 1ull)) continue;
-            if (next + 1 >= wb + kWave) {  // slide the window (wave-uniform)
-                wb = next;
-                rpw = row_ptr[wb + lane <= num_rows ? wb + lane : num_rows];
-            }
-            const int a = __builtin_amdgcn_readlane(rpw, next - wb);
-            const int b = __builtin_amdgcn_readlane(rpw, next + 1 - wb);
-            if (next < num_rows && (int64_t)next + a < d1 && b - a <= lmax) {
-                if (g == gi) {
-                    row = next;
-                    e = a;
-                    ee = b;
-                    div = row_div ? row_div[next] : 1.f;  // arrives long before the flush
-                }
-                ++next;
-            } else {
-                stop = true;
-            }
-        }
+        h.assign<NC>(row < 0, NC, KG, g, lane, [&](int q, int a, int b) {
+            row = q;
+            e = a;
+            ee = b;
+            div = row_div ? row_div[q] : 1.f;  // arrives long before the flush
+        });
     };
     auto load_cw = [&](int (&c)[U], float (&w)[U]) {
 #pragma unroll
@@ -551,7 +529,7 @@ __device__ __forceinline__ int stream_rows(float *acc, int DS, int r,
 #pragma unroll
         for (int u = 0; u < U; ++u) w[u] = wn[u];
     }
-    return next;
+    return h.next;
 }
 
 template <int KG, int U, bool WIDE, bool EMIT, bool STREAM = false>
@@ -587,24 +565,24 @@ __global__ __launch_bounds__(kBlock, EMIT ? MAXK_FWD_EMIT_WAVES : MAXK_FWD_WAVES
     };
     const bool tr = (STREAM || MAXK_FWD_RECORDS_DEEP) && !WIDE && !EMIT && trec != nullptr;
 
+    // The item's range, item_range()'s four lines written out: through the call the streaming
+    // kernels compile to a different block structure and the products-sized forward is 0.18 %
+    // slower (profiles/r09/token_items/ab.md).
     const int64_t total = (int64_t)num_rows + num_e;
     const int64_t d0 = (int64_t)item * chunk;
     const int64_t d1 = d0 + chunk < total ? d0 + chunk : total;
     int r = wave_first_row_token(row_ptr, num_rows, d0);
+    const ItemRange it{d0, d1, r, d0 - r};
 
-    // Continuation of row r-1 (its token precedes d0): edges e with e + r in [d0, d1).
-    // A row of at most `chunk` edges is never split: the item holding its row token walks all
-    // of it, past d1, so only longer (hub) rows leave a continuation and a slab for the fixup
-    // (Reddit-sized k = 16 forward 1.596 -> 1.585 ms, ogbn-products-sized k = 8 3.237 -> 3.19
-    // ms, proteins unchanged; profiles/r04/tune/fwd_snap_rows_ab.txt).  An item then walks at
-    // most 2 * chunk tokens.
+    // Continuation of row r-1 (its token precedes d0), under CutHubRows: a row of at most
+    // `chunk` edges is never split, so only longer (hub) rows leave a continuation and a slab
+    // for the fixup (Reddit-sized k = 16 forward 1.596 -> 1.585 ms, ogbn-products-sized k = 8
+    // 3.237 -> 3.19 ms, proteins unchanged; profiles/r04/tune/fwd_snap_rows_ab.txt).
     int cont = -1;
     if (r > 0) {
-        const int64_t sb = d0 - r;
-        int64_t se = (int64_t)row_ptr[r];
-        if (d1 - r < se) se = d1 - r;
-        const bool whole = (int64_t)row_ptr[r] - row_ptr[r - 1] <= chunk;
-        if (sb < se && !whole) {
+        const RowPiece p = cont_piece(CutHubRows{}, it.p_lo, d1, r, row_ptr[r - 1], row_ptr[r], chunk);
+        const int64_t sb = p.sb, se = p.se;
+        if (sb < se && p.hub) {
             const float div = row_div ? row_div[r - 1] : 1.f;  // loaded before the walk
             wave_lds_fence();
             if (tr)
@@ -621,13 +599,12 @@ __global__ __launch_bounds__(kBlock, EMIT ? MAXK_FWD_EMIT_WAVES : MAXK_FWD_WAVES
 
     // Rows whose token lies in [d0, d1): this item owns them.  row_ptr of 64 consecutive rows
     // sits one per lane (window from row wb), for the short-row test below.
-    int wb = r, rpw = 0;
+    PtrWindow win{row_ptr, num_rows, r, 0};
     constexpr bool BATCH = NC > 1 && !WIDE && !EMIT && !STREAM && MAXK_FWD_SHORT > 0;
-    if constexpr (BATCH)
-        rpw = row_ptr[r + lane <= num_rows ? r + lane : num_rows];
+    if constexpr (BATCH) win.load(r, lane);
     while (r < num_rows) {
         int64_t rb = row_ptr[r];
-        if (rb + r >= d1) break;
+        if (!row_owned(d1, r, rb)) break;
         if constexpr (STREAM) {
             // every row of at most MAXK_FWD_STREAM edges by the streaming lane groups; a longer
             // one (or the item's end) stops them, and the wave walks it below
@@ -645,7 +622,7 @@ __global__ __launch_bounds__(kBlock, EMIT ? MAXK_FWD_EMIT_WAVES : MAXK_FWD_WAVES
             }
             if (r >= num_rows) break;
             rb = row_ptr[r];
-            if (rb + r >= d1) break;
+            if (!row_owned(d1, r, rb)) break;
         }
         if (BATCH && !tr) {
             // Short-row batch: up to NC consecutive rows, each wholly inside the item and at
@@ -653,12 +630,9 @@ __global__ __launch_bounds__(kBlock, EMIT ? MAXK_FWD_EMIT_WAVES : MAXK_FWD_WAVES
             // loads in flight instead of walking one short row at a time (Flickr: avg
             // degree 11).  The test reads the row_ptr window (no load per row): long rows
             // pay only a few shuffles for it.
-            if (r + NC >= wb + kWave) {  // slide the window
-                wb = r;
-                rpw = row_ptr[r + lane <= num_rows ? r + lane : num_rows];
-            }
+            win.slide(r, lane, NC);  // entries r .. r + NC (read per lane: __shfl, not readlane)
             const int rq = r + lane;
-            const int rpj = __shfl(rpw, (r - wb + lane) & (kWave - 1));
+            const int rpj = __shfl(win.v, (r - win.wb + lane) & (kWave - 1));
             const int rpn = __shfl_down(rpj, 1);
             const bool okj = lane < NC && rq < num_rows && (int64_t)rq + rpn < d1 &&
                              rpn - rpj <= MAXK_FWD_SHORT;
@@ -690,8 +664,7 @@ __global__ __launch_bounds__(kBlock, EMIT ? MAXK_FWD_EMIT_WAVES : MAXK_FWD_WAVES
                 continue;
             }
         }
-        int64_t se = (int64_t)row_ptr[r + 1];
-        if (d1 - r - 1 < se && se - rb > chunk) se = d1 - r - 1;  // a hub row: split
+        const int64_t se = row_piece(CutHubRows{}, d1, r, rb, row_ptr[r + 1], chunk).se;
         const float div = row_div ? row_div[r] : 1.f;  // loaded before the walk
         wave_lds_fence();
         if (rb < se && tr)
@@ -742,8 +715,7 @@ FwdLayout fwd_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, i
                D % 4 == 0 && num_e < kFwdSparseDegree * num_rows;
     L.chunk = fwd_chunk(num_rows, num_e, chunk,
                         fwd_resident_waves(L.kg, L.DS, L.deep ? 4 : L.stream ? 5 : 7));
-    const int64_t n = ceil_div(num_rows + num_e, L.chunk);
-    L.n_items = (int)(n > 0 ? n : 1);
+    L.n_items = token_items(num_rows, num_e, L.chunk);
     L.rec_off = 0;
     L.rec_bytes = al256((size_t)num_cols * L.RS);
     L.slab_off = L.rec_off + L.rec_bytes;

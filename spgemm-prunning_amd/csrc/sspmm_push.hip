@@ -6,9 +6,10 @@
 // stores, so the 7.3 GB stream does not evict the selector table every edge gathers from).
 // The csc phase 2 (maxk_sspmm_backward_csc) gathers a destination's rows through the CSC
 // permutation and sums them in a fixed order.
-// Both phases use the token-stream work partition of common.h (one wave per item of C
-// tokens, hub rows split, short rows batched); loads-in-flight depth per launch from the
-// average degree (pick_depth).
+// Both phases use the token-stream work partition of token_items.h (one wave per item of C
+// tokens) under its cut-at-the-item's-end rule: an item walks exactly the edges, or CSC slots,
+// whose tokens it holds.  Loads-in-flight depth per launch from the average degree
+// (pick_depth).
 #include "sspmm_bwd.h"
 
 namespace maxk {
@@ -270,19 +271,15 @@ __global__ __launch_bounds__(kBlock, MAXK_BWD_WAVES) void sspmm_bwd_kernel(
     float *g_lds = lds[wid];
     *reinterpret_cast<float4 *>(&g_lds[lane * 4]) = make_float4(0.f, 0.f, 0.f, 0.f);
 
-    const int64_t total = (int64_t)num_rows + num_e;
-    const int64_t d0 = (int64_t)item * chunk;
-    const int64_t d1 = d0 + chunk < total ? d0 + chunk : total;
-    int r = wave_first_row_token(row_ptr, num_rows, d0);
-    // Rows q = r-1 (continuation), r, r+1, ...: the item's edges of row q are
-    // [max(rb, d0-q-1), min(re, d1-q-1)).  row_ptr / row_div of 64 consecutive rows sit
-    // one per lane (read with readlane), and each row's G values (4 per lane, columns
-    // lane + 64*i) are loaded while the previous row's edges are pushed: no per-row
-    // dependent load before a row can start.
-    int q = r > 0 ? r - 1 : 0;
-    int wb = q;
-    int rpw = row_ptr[wb + lane < num_rows ? wb + lane : num_rows];
-    float dvw = row_div ? row_div[wb + lane < num_rows ? wb + lane : num_rows - 1] : 1.f;
+    const ItemRange it = item_range(row_ptr, num_rows, num_e, item, chunk);
+    // Rows q = r-1 (continuation), r, r+1, ...: each one's piece under CutAtEnd.  row_ptr /
+    // row_div of 64 consecutive rows sit one per lane (read with readlane), and each row's G
+    // values (4 per lane, columns lane + 64*i) are loaded while the previous row's edges are
+    // pushed: no per-row dependent load before a row can start.
+    int q = it.r > 0 ? it.r - 1 : 0;
+    PtrWindow win{row_ptr, num_rows, 0, 0};
+    win.load(q, lane);
+    float dvw = row_div ? row_div[q + lane < num_rows ? q + lane : num_rows - 1] : 1.f;
     auto load_g = [&](int row, float (&g)[4]) {
         const float *gr = grad + (int64_t)(row < num_rows ? row : num_rows - 1) * D;
 #pragma unroll
@@ -294,23 +291,19 @@ __global__ __launch_bounds__(kBlock, MAXK_BWD_WAVES) void sspmm_bwd_kernel(
     float gn[4];
     load_g(q, gn);
     for (; q < num_rows; ++q) {
-        if (q + 1 - wb >= kWave) {  // slide the window
-            wb = q;
-            rpw = row_ptr[wb + lane < num_rows ? wb + lane : num_rows];
-            if (row_div) dvw = row_div[wb + lane < num_rows ? wb + lane : num_rows - 1];
-        }
-        const int rb = __builtin_amdgcn_readlane(rpw, q - wb);
-        const int re = __builtin_amdgcn_readlane(rpw, q + 1 - wb);
-        if ((int64_t)q + rb >= d1) break;
+        if (win.slide(q, lane) && row_div)  // the divisor window moves with it
+            dvw = row_div[q + lane < num_rows ? q + lane : num_rows - 1];
+        const int rb = win.begin(q);
+        const int re = win.end(q);
+        if (!row_owned(it.d1, q, rb)) break;
         float g[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) g[i] = gn[i];
         if (q + 1 < num_rows) load_g(q + 1, gn);
-        const int64_t sb64 = d0 - q - 1 > rb ? d0 - q - 1 : rb;
-        const int64_t se64 = d1 - q - 1 < re ? d1 - q - 1 : re;
-        if (sb64 >= se64) continue;
+        const RowPiece p = any_piece(CutAtEnd{}, it.d0, it.d1, q, rb, re);
+        if (p.sb >= p.se) continue;
         const float div = __builtin_bit_cast(
-            float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, dvw), q - wb));
+            float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, dvw), q - win.wb));
         wave_lds_fence();
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -318,8 +311,8 @@ __global__ __launch_bounds__(kBlock, MAXK_BWD_WAVES) void sspmm_bwd_kernel(
             if (j < D) g_lds[j] = row_div ? g[i] / div : g[i];
         }
         wave_lds_fence();
-        push_edges<KG, U, MODE>(g_lds, col_idx, edge_val, cbsr_idx, dst, (int)num_e, (int)sb64,
-                                (int)se64, k, lane, esel);
+        push_edges<KG, U, MODE>(g_lds, col_idx, edge_val, cbsr_idx, dst, (int)num_e, (int)p.sb,
+                                (int)p.se, k, lane, esel);
     }
 }
 
@@ -391,9 +384,10 @@ __device__ __forceinline__ void segment_sum(const float *__restrict__ T, EidAt e
 // Each lane group of LR = k/4 lanes walks one destination's slots U at a time into its own
 // float4 (in slot order: bitwise the same run to run), stores the row the step it ends and takes
 // the item's next destination, so 64/LR destinations are in flight per wave; the next step's
-// gathers are issued before this step's sums.  Destinations are taken in order while owned by
-// the item (token < d1) and holding at most lmax of its slots; returns the first one not taken
-// (the caller sums a longer one with the whole wave).  k % 4 == 0.
+// gathers are issued before this step's sums.  Destinations are handed out by
+// RowHandout<CutAtEnd> (token_items.h): in order while owned by the item and holding at most
+// lmax of its slots; returns the first one not taken (the caller sums a longer one with the
+// whole wave).  k % 4 == 0.
 template <int U, bool NT = false, typename EidAt>
 __device__ __forceinline__ int csc_groups(const float *__restrict__ T, EidAt eid_at,
                                           const int32_t *__restrict__ col_ptr, int c,
@@ -402,34 +396,15 @@ __device__ __forceinline__ int csc_groups(const float *__restrict__ T, EidAt eid
     const int LR = k / 4, NG = kWave / LR;
     const int g = lane / LR, q = lane % LR;
     const float4 *__restrict__ T4 = reinterpret_cast<const float4 *>(T);
-    int wb = c;  // col_ptr window: destinations [wb, wb + 64), one per lane
-    int cpw = col_ptr[wb + lane <= num_cols ? wb + lane : num_cols];
-    int next = c;       // the next destination to hand out (wave-uniform)
-    bool stop = false;  // it is not the item's or is too long (wave-uniform)
-    int dst = -1;       // this group's destination and its slot range [t, te)
+    RowHandout<CutAtEnd> h(col_ptr, num_cols, c, d1, lmax, lane);
+    int dst = -1;  // this group's destination and its slot range [t, te)
     int64_t t = 0, te = 0;
     auto assign = [&]() {
-        const uint64_t idle = __ballot(dst < 0);
-        for (int gi = 0; gi < NG && !stop; ++gi) {
-            if (!((idle >> (gi * LR)) & 1ull)) continue;
-            if (next + 1 >= wb + kWave) {  // slide the window (wave-uniform)
-                wb = next;
-                cpw = col_ptr[wb + lane <= num_cols ? wb + lane : num_cols];
-            }
-            const int64_t cb = __builtin_amdgcn_readlane(cpw, next - wb);
-            int64_t se = __builtin_amdgcn_readlane(cpw, next + 1 - wb);
-            if (d1 - next - 1 < se) se = d1 - next - 1;
-            if (next < num_cols && next + cb < d1 && se - cb <= lmax) {
-                if (g == gi) {
-                    dst = next;
-                    t = cb;
-                    te = se;
-                }
-                ++next;
-            } else {
-                stop = true;
-            }
-        }
+        h.assign<1>(dst < 0, NG, LR, g, lane, [&](int col, int cb, int ce) {
+            dst = col;
+            t = cb;
+            te = ce;
+        });
     };
     auto gather = [&](float4 (&v)[U]) {
 #pragma unroll
@@ -463,7 +438,7 @@ __device__ __forceinline__ int csc_groups(const float *__restrict__ T, EidAt eid
             a = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-    return next;
+    return h.next;
 }
 
 // STAGED (chunk <= kCscStage): the item's CSC slots are one contiguous range of csc_eid,
@@ -491,11 +466,9 @@ __global__ __launch_bounds__(kBlock) void csc_sum_kernel(const int32_t *__restri
                                        : xcd_contiguous_block(blockIdx.x, gridDim.x);
     const int item = blk * kWavesPerBlock + wid;
     if (item >= n_items) return;
-    const int64_t total = (int64_t)num_cols + num_e;
-    const int64_t d0 = (int64_t)item * chunk;
-    const int64_t d1 = d0 + chunk < total ? d0 + chunk : total;
-    int c = wave_first_row_token(col_ptr, num_cols, d0);
-    const int64_t p_lo = d0 - c;  // the item's first CSC slot
+    const ItemRange it = item_range(col_ptr, num_cols, num_e, item, chunk);
+    const int64_t d1 = it.d1, p_lo = it.p_lo;  // p_lo: the item's first CSC slot
+    int c = it.r;
     int32_t *se_lds = s_eid + (STAGED ? wid * chunk : 0);
     if constexpr (STAGED) {
         const int n_pos = (int)(num_e - p_lo < chunk ? num_e - p_lo : chunk);
@@ -510,11 +483,9 @@ __global__ __launch_bounds__(kBlock) void csc_sum_kernel(const int32_t *__restri
     };
     int cont = -1;
     if (c > 0) {
-        const int64_t sb = p_lo;
-        int64_t se = (int64_t)col_ptr[c];
-        if (d1 - c < se) se = d1 - c;
-        if (sb < se) {
-            segment_sum<VEC, KG, U, NT>(T, eid_at, sb, se, k, slab + (int64_t)item * k, lane);
+        const RowPiece p = cont_piece(CutAtEnd{}, it.p_lo, d1, c, col_ptr[c]);
+        if (p.sb < p.se) {
+            segment_sum<VEC, KG, U, NT>(T, eid_at, p.sb, p.se, k, slab + (int64_t)item * k, lane);
             cont = c - 1;
         }
     }
@@ -526,10 +497,9 @@ __global__ __launch_bounds__(kBlock) void csc_sum_kernel(const int32_t *__restri
             if (c >= num_cols) break;
         }
         const int64_t cb = col_ptr[c];
-        if (cb + c >= d1) break;
-        int64_t se = (int64_t)col_ptr[c + 1];
-        if (d1 - c - 1 < se) se = d1 - c - 1;
-        segment_sum<VEC, KG, U, NT>(T, eid_at, cb, se, k, grad_cbsr + (int64_t)c * k, lane);
+        if (!row_owned(d1, c, cb)) break;
+        const RowPiece p = row_piece(CutAtEnd{}, d1, c, cb, col_ptr[c + 1]);
+        segment_sum<VEC, KG, U, NT>(T, eid_at, p.sb, p.se, k, grad_cbsr + (int64_t)c * k, lane);
     }
 }
 
@@ -540,11 +510,6 @@ int bwd_chunk(int64_t num_rows, int64_t num_e, int32_t chunk, int per_slot) {
     int64_t c = ceil_div(total, device_cus() * 32 * per_slot);
     c = c < 256 ? 256 : (c > 2048 ? 2048 : c);
     return (int)c;
-}
-
-int n_items_for(int64_t rows, int64_t num_e, int chunk) {
-    const int64_t n = ceil_div(rows + num_e, chunk);
-    return (int)(n > 0 ? n : 1);
 }
 
 // Loads in flight per lane ("depth" U): one wave step covers `per_step` edges (or
@@ -564,7 +529,7 @@ int launch_push(hipStream_t s, const int32_t *row_ptr, const int32_t *col_idx,
                 const float *edge_val, const float *grad, const float *row_div,
                 const uint8_t *cbsr_idx, float *dst, int nr, int64_t num_cols, int64_t num_e,
                 int D, int k, int chunk, const uint8_t *esel = nullptr) {
-    const int n_items = n_items_for(nr, num_e, chunk);
+    const int n_items = token_items(nr, num_e, chunk);
     const int64_t blocks = ceil_div(n_items, kWavesPerBlock);
     const dim3 grid((unsigned)(MAXK_P1_XCD ? xcd_grid(blocks) : blocks));
     if (MODE == kStore && ((MAXK_BWD_X4 && k % 4 == 0) || esel)) {
@@ -612,7 +577,7 @@ struct CscLayout {
 CscLayout csc_layout(int64_t num_cols, int64_t num_e, int k, int chunk) {
     CscLayout L{};
     L.chunk = bwd_chunk(num_cols, num_e, chunk, MAXK_P2_ITEMS);
-    L.n_items = n_items_for(num_cols, num_e, L.chunk);
+    L.n_items = token_items(num_cols, num_e, L.chunk);
     L.t_bytes = al256((size_t)(num_e + 1) * k * sizeof(float));  // + dummy row for masked lanes
     L.slab_off = L.t_bytes;
     L.row_off = L.slab_off + al256((size_t)L.n_items * k * sizeof(float));
