@@ -188,6 +188,81 @@ int maxk_edge_weight_grad(const int32_t *row_ptr, const int32_t *col_idx, const 
                           void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Edge softmax: the weights of a destination's incoming edges, normalised over its CSR row,
+ * and their backward -- what produces the edge weights maxk_spgemm_forward takes and consumes
+ * the gradient maxk_edge_weight_grad returns.  The reference has no counterpart.
+ * Edge e lies in CSR row r, c = col_idx[e].
+ *   GAT form      z_e = s_dst[r] + s_src[c],  l_e = z_e > 0 ? z_e : negative_slope * z_e
+ *   plain form    l_e = logits[e]
+ *   forward       w_e = exp(l_e - m_r) / sum_{j in r} exp(l_j - m_r),  m_r = max_{j in r} l_j
+ *   backward      t_r = sum_{e in r} w_e * grad_w_e,   gl_e = w_e * (grad_w_e - t_r)
+ *                 plain form: grad_logits[e] = gl_e
+ *                 GAT form:   gz_e = gl_e * (z_e > 0 ? 1 : negative_slope), z recomputed from
+ *                             the scores; grad_s_dst[r] = sum_{e in r} gz_e;
+ *                             grad_s_src[c] = sum_{e: col_idx[e] = c} gz_e, through the graph's
+ *                             transpose plan (col_ptr, csc_eid) in CSC slot order
+ * s_dst f32 [num_rows], s_src f32 [num_cols], logits / w / grad_w / grad_logits f32 [num_e] in
+ * CSR order; negative_slope in [0, 1].  The plain form reads no column, num_cols only has to be
+ * >= 0.  num_e < 2^31, any num_rows and num_cols; num_e == 0 launches nothing and succeeds (the
+ * GAT backward then writes zeros to both gradients).
+ * Work partition: token-stream items of chunk_edges tokens, one wavefront each; a row cut over
+ *   items is merged from per-item partials in item order, so a hub row costs no wave more than
+ *   one item.  chunk_edges: 0 = the forward's auto rule for large graphs, about 8 items per
+ *   resident wave slot in [256, 2048] tokens.
+ * Numerics (tests/edge_softmax_ref.py; u = 2^-24, n_r the row's degree, A_r = max_e |z_e| or
+ *   max_e |logits[e]|):
+ *     |w - exact| <= (n_r + 16 + 16 A_r) * u * exact + (n_r + 16) * 2^-149
+ *   (the exponent's argument is rounded three times, each at most 2 A_r u; exp is good to a
+ *   few ulp; n_r terms; one division; the floor covers weights that underflow), gl within
+ *   (n_r + 8) * u * |w_e| * (|grad_w_e| + sum_j |w_j grad_w_j|) plus w's own bound carried
+ *   through, and each score gradient within (n + 8) * u * sum|terms| on top of its terms'
+ *   bounds, n its number of addends; an element without addends (a row without edges, a
+ *   column no edge reads) is exactly 0.  A row of one edge gives exactly w = 1 and gl = 0.
+ *   Every sum has a fixed order and nothing is added atomically: both directions are bitwise
+ *   repeatable for equal arguments, chunk_edges included; another chunk_edges groups a cut
+ *   row's sums differently, so results may differ between chunk sizes within the bound.
+ * Non-finite values follow the IEEE evaluation of the formulas, as torch.softmax does: a row
+ *   holding a NaN or a +Inf logit is all NaN; a -Inf logit gives exactly 0 unless every logit of
+ *   the row is -Inf, then the row is all NaN; a NaN in s_src[c] reaches every row that reads
+ *   column c and no other, and a NaN in a column no edge reads reaches nothing.
+ * Memory, as the top comment: the workspace (per-item partials of the cut rows; for the GAT
+ *   backward also gz [num_e] and the column side's partials) is exactly the queried size, 256-B
+ *   aligned, and may hold anything; a shorter one is rejected with MAXK_ERR_INVALID ("workspace
+ *   too small") on the host before anything is launched; w, grad_logits, grad_s_dst [num_rows]
+ *   and grad_s_src [num_cols] are fully written (w: every edge; rows without edges write
+ *   nothing); inputs are never written; nothing else is touched; no output may alias an input.
+ *   The forward stages the logits in w before it normalises them.
+ * Argument errors (null pointer, negative size, negative_slope outside [0, 1] or NaN):
+ *   MAXK_ERR_INVALID with a message, before any launch.
+ * ------------------------------------------------------------------------- */
+size_t maxk_edge_softmax_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                        int32_t chunk_edges);
+int maxk_edge_softmax(const int32_t *row_ptr, const float *logits, float *w, int64_t num_rows,
+                      int64_t num_cols, int64_t num_e, int32_t chunk_edges, void *workspace,
+                      size_t workspace_bytes, void *stream);
+size_t maxk_edge_softmax_backward_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                 int64_t num_e, int32_t chunk_edges);
+int maxk_edge_softmax_backward(const int32_t *row_ptr, const float *w, const float *grad_w,
+                               float *grad_logits, int64_t num_rows, int64_t num_cols,
+                               int64_t num_e, int32_t chunk_edges, void *workspace,
+                               size_t workspace_bytes, void *stream);
+size_t maxk_gat_edge_softmax_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                            int32_t chunk_edges);
+int maxk_gat_edge_softmax(const int32_t *row_ptr, const int32_t *col_idx, const float *s_dst,
+                          const float *s_src, float negative_slope, float *w, int64_t num_rows,
+                          int64_t num_cols, int64_t num_e, int32_t chunk_edges, void *workspace,
+                          size_t workspace_bytes, void *stream);
+size_t maxk_gat_edge_softmax_backward_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                     int64_t num_e, int32_t chunk_edges);
+int maxk_gat_edge_softmax_backward(const int32_t *row_ptr, const int32_t *col_idx,
+                                   const int32_t *col_ptr, const int32_t *csc_eid,
+                                   const float *s_dst, const float *s_src, float negative_slope,
+                                   const float *w, const float *grad_w, float *grad_s_dst,
+                                   float *grad_s_src, int64_t num_rows, int64_t num_cols,
+                                   int64_t num_e, int32_t chunk_edges, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Backward outer-product sampled SpMM (SSpMM):
  *   grad_cbsr[c,l] = sum_{e=(r->c)} edge_val[e] * grad_out[r, cbsr_idx[c,l]] / row_div[r]
  *                  = (A^T diag(1/row_div) G)[c, cbsr_idx[c,l]]     (from the CSR of A)

@@ -46,6 +46,7 @@ __all__ = [
     "topk_cbsr", "cbsr_scatter_dense", "topk_cbsr_dense", "topk_backward", "topk_error_rows",
     "build_warp4_metadata", "warp4_to_indptr",
     "spgemm_forward", "sspmm_backward", "edge_weight_grad", "graph_only_mode", "DenseSpMMPlan",
+    "edge_softmax", "edge_softmax_backward", "gat_edge_softmax", "gat_edge_softmax_backward",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -330,6 +331,145 @@ def edge_weight_grad(indptr: torch.Tensor, indices: torch.Tensor, cbsr_val: torc
                (_ptr(indptr), _ptr(indices), _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(grad_output),
                 _ptr(row_div), _ptr(out), *shape))
     return out
+
+
+def _validate_rows(validate, indptr, indices, num_cols, num_e):
+    """The edge softmax's graph check, under the rules of _validate_call: the CSR's ranges once
+    per graph by default (indices None: the plain form, which reads no column -- row_ptr alone,
+    every call it is asked for), never inside a capture."""
+    if validate is False or torch.cuda.is_current_stream_capturing():
+        return
+    always = validate if validate is not None else _validate_default()
+    if indices is None:
+        if always or _validate_mode() == "once":
+            def build():
+                if indptr.numel() == 0 or int(indptr[0]) != 0 or int(indptr[-1]) != num_e:
+                    raise RuntimeError(f"row_ptr must start at 0 and end at num_e={num_e}")
+                if bool((indptr[1:] < indptr[:-1]).any()):
+                    raise RuntimeError("row_ptr must be non-decreasing")
+                return True
+            if always:
+                build()
+            else:
+                _CHECKED.get((indptr,), (int(num_e),), build)
+    elif always:
+        _validate_graph(indptr, indices, num_cols, num_e)
+    elif _validate_mode() == "once":
+        _check_graph_once(indptr, indices, num_cols)
+
+
+def _edge_vector(out, E, dev, name="out"):
+    if out is None:
+        return torch.empty(E, dtype=torch.float32, device=dev)
+    _need(out, name, torch.float32)
+    if tuple(out.shape) != (E,):
+        raise RuntimeError(f"{name} must be [num_e]")
+    return out
+
+
+def edge_softmax(indptr: torch.Tensor, logits: torch.Tensor, chunk: int = 0,
+                 out: Optional[torch.Tensor] = None,
+                 validate: Optional[bool] = None) -> torch.Tensor:
+    """w[E] float32: the softmax of `logits` over every CSR row (a destination's incoming edges),
+    maxk_edge_softmax.  Rows without edges write nothing; bitwise repeatable."""
+    _need(indptr, "indptr", torch.int32)
+    _need(logits, "logits", torch.float32)
+    E = logits.numel()
+    if logits.dim() != 1:
+        raise RuntimeError("logits must be [num_e]")
+    _validate_rows(validate, indptr, None, 0, E)
+    dev = logits.device
+    out = _edge_vector(out, E, dev)
+    shape = (indptr.numel() - 1, 0, E, chunk)
+    _launch_ws(dev, "maxk_edge_softmax", "maxk_edge_softmax_workspace_size", shape,
+               (_ptr(indptr), _ptr(logits), _ptr(out), *shape))
+    return out
+
+
+def edge_softmax_backward(indptr: torch.Tensor, w: torch.Tensor, grad_w: torch.Tensor,
+                          chunk: int = 0, out: Optional[torch.Tensor] = None,
+                          validate: Optional[bool] = None) -> torch.Tensor:
+    """grad_logits[E] = w * (grad_w - sum over the row of w * grad_w), from the forward's w
+    (maxk_edge_softmax_backward); no atomics, bitwise repeatable."""
+    _need(indptr, "indptr", torch.int32)
+    _need(w, "w", torch.float32)
+    _need(grad_w, "grad_w", torch.float32)
+    E = w.numel()
+    if w.dim() != 1 or grad_w.shape != w.shape:
+        raise RuntimeError("w and grad_w must be [num_e]")
+    _validate_rows(validate, indptr, None, 0, E)
+    dev = w.device
+    out = _edge_vector(out, E, dev)
+    shape = (indptr.numel() - 1, 0, E, chunk)
+    _launch_ws(dev, "maxk_edge_softmax_backward", "maxk_edge_softmax_backward_workspace_size",
+               shape, (_ptr(indptr), _ptr(w), _ptr(grad_w), _ptr(out), *shape))
+    return out
+
+
+def _gat_operands(indptr, indices, s_dst, s_src):
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (s_dst, "s_dst", torch.float32), (s_src, "s_src", torch.float32)):
+        _need(t, n, dt)
+    num_rows = indptr.numel() - 1
+    if s_dst.dim() != 1 or s_dst.numel() != num_rows:
+        raise RuntimeError("s_dst must be [num_rows]")
+    if s_src.dim() != 1:
+        raise RuntimeError("s_src must be [num_cols]")
+    return num_rows, s_src.numel(), indices.numel()
+
+
+def gat_edge_softmax(indptr: torch.Tensor, indices: torch.Tensor, s_dst: torch.Tensor,
+                     s_src: torch.Tensor, negative_slope: float = 0.2, chunk: int = 0,
+                     out: Optional[torch.Tensor] = None,
+                     validate: Optional[bool] = None) -> torch.Tensor:
+    """w[E] float32: the softmax over every CSR row of leaky_relu(s_dst[row] + s_src[indices[e]])
+    (maxk_gat_edge_softmax): the attention coefficients of a single GAT head, from the two score
+    vectors, without an E-sized intermediate.  Bitwise repeatable."""
+    num_rows, num_cols, E = _gat_operands(indptr, indices, s_dst, s_src)
+    _validate_rows(validate, indptr, indices, num_cols, E)
+    dev = s_src.device
+    out = _edge_vector(out, E, dev)
+    shape = (num_rows, num_cols, E, chunk)
+    _launch_ws(dev, "maxk_gat_edge_softmax", "maxk_gat_edge_softmax_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(s_dst), _ptr(s_src), float(negative_slope),
+                _ptr(out), *shape))
+    return out
+
+
+def gat_edge_softmax_backward(indptr: torch.Tensor, indices: torch.Tensor, s_dst: torch.Tensor,
+                              s_src: torch.Tensor, w: torch.Tensor, grad_w: torch.Tensor,
+                              negative_slope: float = 0.2, chunk: int = 0,
+                              out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                              validate: Optional[bool] = None):
+    """(grad_s_dst [num_rows], grad_s_src [num_cols]) of gat_edge_softmax from its w and the
+    gradient of w (maxk_gat_edge_softmax_backward).  The column sums go through the graph's
+    transpose plan (transpose_plan, cached per `indices`) in CSC slot order: no atomics, bitwise
+    repeatable; every element is written, 0 for a row without edges and a column no edge
+    reads."""
+    num_rows, num_cols, E = _gat_operands(indptr, indices, s_dst, s_src)
+    _need(w, "w", torch.float32)
+    _need(grad_w, "grad_w", torch.float32)
+    if tuple(w.shape) != (E,) or tuple(grad_w.shape) != (E,):
+        raise RuntimeError("w and grad_w must be [num_e]")
+    _validate_rows(validate, indptr, indices, num_cols, E)
+    dev = s_src.device
+    col_ptr, csc_eid = transpose_plan(indices, num_cols)
+    if out is None:
+        g_dst = torch.empty(num_rows, dtype=torch.float32, device=dev)
+        g_src = torch.empty(num_cols, dtype=torch.float32, device=dev)
+    else:
+        g_dst, g_src = out
+        _need(g_dst, "out[0]", torch.float32)
+        _need(g_src, "out[1]", torch.float32)
+        if tuple(g_dst.shape) != (num_rows,) or tuple(g_src.shape) != (num_cols,):
+            raise RuntimeError("out must be ([num_rows], [num_cols])")
+    shape = (num_rows, num_cols, E, chunk)
+    _launch_ws(dev, "maxk_gat_edge_softmax_backward",
+               "maxk_gat_edge_softmax_backward_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(s_dst),
+                _ptr(s_src), float(negative_slope), _ptr(w), _ptr(grad_w), _ptr(g_dst),
+                _ptr(g_src), *shape))
+    return g_dst, g_src
 
 
 def records_ok(num_rows: int, num_cols: int, num_e: int, dim_origin: int, k: int) -> bool:

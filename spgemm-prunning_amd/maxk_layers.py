@@ -329,6 +329,101 @@ class MaxKGINConv(nn.Module):
         return rst
 
 
+class EdgeSoftmax(Function):
+    """w = softmax of per-edge logits over every destination's incoming edges (the CSR row),
+    both directions in HIP (maxk_edge_softmax / _backward): no E-sized intermediates, no
+    atomics, bitwise repeatable."""
+
+    @staticmethod
+    def forward(ctx, indptr, logits):
+        w = mk.edge_softmax(indptr, logits.float().contiguous())
+        ctx.save_for_backward(indptr, w)
+        ctx.dtype = logits.dtype
+        return w.to(logits.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_w):
+        indptr, w = ctx.saved_tensors
+        g = mk.edge_softmax_backward(indptr, w, grad_w.float().contiguous())
+        return None, g.to(ctx.dtype)
+
+
+class GATEdgeSoftmax(Function):
+    """alpha = softmax over the row of leaky_relu(s_dst[row] + s_src[col]): a GAT head's
+    attention coefficients from its two score vectors (maxk_gat_edge_softmax / _backward).
+    Saves alpha and the scores; the backward recomputes the sign of the pre-activation."""
+
+    @staticmethod
+    def forward(ctx, indptr, indices, s_dst, s_src, negative_slope):
+        sd, ss = s_dst.float().contiguous(), s_src.float().contiguous()
+        w = mk.gat_edge_softmax(indptr, indices, sd, ss, negative_slope)
+        ctx.save_for_backward(indptr, indices, sd, ss, w)
+        ctx.slope = float(negative_slope)
+        ctx.dtypes = (s_dst.dtype, s_src.dtype)
+        return w
+
+    @staticmethod
+    def backward(ctx, grad_w):
+        indptr, indices, sd, ss, w = ctx.saved_tensors
+        g_dst, g_src = mk.gat_edge_softmax_backward(indptr, indices, sd, ss, w,
+                                                    grad_w.float().contiguous(), ctx.slope)
+        return None, None, g_dst.to(ctx.dtypes[0]), g_src.to(ctx.dtypes[1]), None
+
+
+def edge_softmax(graph: CSRGraph, logits: torch.Tensor) -> torch.Tensor:
+    """Softmax of logits [E] (CSR order) over each destination's incoming edges."""
+    return EdgeSoftmax.apply(graph.indptr, logits)
+
+
+def gat_edge_softmax(graph: CSRGraph, s_dst: torch.Tensor, s_src: torch.Tensor,
+                     negative_slope: float = 0.2) -> torch.Tensor:
+    """alpha [E] float32 of a single GAT head: s_dst [V] scores the destinations, s_src [V] the
+    sources."""
+    return GATEdgeSoftmax.apply(graph.indptr, graph.indices, s_dst, s_src, negative_slope)
+
+
+class MaxKGATConv(nn.Module):
+    """Single-head GAT on MaxK features:
+    rst[v] = sum_{u in N(v)} alpha_vu fc(x_sparse[u]) + b,
+    alpha_v. = softmax_u leaky_relu(attn_dst . fc(x_sparse[v]) + attn_src . fc(x_sparse[u])).
+    As everywhere here the aggregation runs on the CBSR and the Linear after it (equal by
+    linearity); the scores are x_sparse @ (fc.weight^T attn), two [V] vectors, and the
+    coefficients come from them in one HIP pass (gat_edge_softmax).  Gradients reach fc.weight
+    and both attention vectors, x_sparse through the scores and topk_values through the
+    aggregation (its feature backward, edge_weight_grad and the softmax backward).  The
+    reference has no GAT: there is no reference_compat."""
+
+    def __init__(self, in_feats: int, out_feats: int, negative_slope: float = 0.2,
+                 bias: bool = True, activation=None):
+        super().__init__()
+        self.in_feats, self.out_feats = in_feats, out_feats
+        self.negative_slope = float(negative_slope)
+        self.fc = nn.Linear(in_feats, out_feats, bias=False)
+        self.attn_src = nn.Parameter(torch.empty(out_feats))
+        self.attn_dst = nn.Parameter(torch.empty(out_feats))
+        self.bias = nn.Parameter(torch.zeros(out_feats)) if bias else None
+        self.activation = activation
+        gain = nn.init.calculate_gain("relu")  # as the usual GATConv: Xavier-normal, ReLU gain
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        with torch.no_grad():
+            nn.init.xavier_normal_(self.attn_src.view(1, -1), gain=gain)
+            nn.init.xavier_normal_(self.attn_dst.view(1, -1), gain=gain)
+
+    def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices):
+        # attn . fc(x) = x . (fc.weight^T attn): both scores from one [V, in] x [in, 2] product
+        v = self.fc.weight.t() @ torch.stack((self.attn_dst, self.attn_src), 1)
+        s = x_sparse @ v
+        alpha = gat_edge_softmax(graph, s[:, 0], s[:, 1], self.negative_slope)
+        agg = graph.aggregate(topk_values, topk_indices, self.in_feats, values=alpha,
+                              row_div=None)
+        rst = linear(agg, self.fc)
+        if self.bias is not None:
+            rst = rst + self.bias
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst
+
+
 class MaxKSAGE(nn.Module):
     """lin_in -> [MaxK -> MaxKSAGEConv] x L -> lin_out (model_integrated_v3.py:522-588; same
     constructor arguments; graph_name is accepted and unused: no schedule files are needed)."""
