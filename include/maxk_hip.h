@@ -188,6 +188,71 @@ int maxk_edge_weight_grad(const int32_t *row_ptr, const int32_t *col_idx, const 
                           void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Multi-head aggregation: H = num_heads forwards, and their edge-weight gradients, over one
+ * graph and one CBSR, differing only in the edge weights -- the attention heads of a GAT.  One
+ * packed record is gathered per edge and serves every head, where H single-head calls gather it
+ * H times.  The reference has no counterpart (it has no attention at all).
+ * Layout, head-major, so every head's slice is a contiguous array the single-head entries take:
+ *   edge_val, grad_edge  f32 [num_heads, num_e], CSR order inside a head;
+ *   out, grad_out        f32 [num_heads, num_rows, dim_origin];
+ *   row_div              f32 [num_rows] shared by the heads, or NULL.
+ * 1 <= num_heads <= MAXK_MAX_HEADS, any value in the range.
+ * ------------------------------------------------------------------------- */
+#define MAXK_MAX_HEADS 8
+
+/* out[h, r, cbsr_idx[c,l]] += edge_val[h, e] * cbsr_val[c,l] / row_div[r]   for every head h
+ * (e in row r, c = col_idx[e]): maxk_spgemm_forward per head.  The reference has no counterpart.
+ * Every output row of every head is written (rows without edges get zeros; num_e == 0 writes
+ * zeros to all of out): no zero-init of out is needed.  No global and no LDS atomics; a hub row
+ * cut over work items is merged from per-item partials in item order.
+ * Shapes: any 1 <= dim_k <= dim_origin <= 256 (dim_k % 4 != 0, odd dim_origin, dim_k > 64).
+ *   There is no dense route and no _sel / _accumulate / records form; a table past 2^24 columns
+ *   or 4 GiB of packed records is rejected with MAXK_ERR_INVALID.
+ * Numerics, in the words of the top comment: every element is within (n + 8) * 2^-24 *
+ *   sum|terms| of exact arithmetic (plus the subnormal floor); the sum order is fixed by the
+ *   graph, chunk_edges, dim_k and num_heads, so the result is bitwise repeatable; the slice of
+ *   head h holds only products with head h's weights and does not depend, bitwise, on the other
+ *   heads' weights; Inf and NaN in cbsr_val propagate per head as in maxk_spgemm_forward.
+ * Memory, as the top comment: the workspace (packed records, per-head split-row slabs) is
+ *   exactly the queried size, 256-B aligned, and may hold anything; a shorter one is rejected
+ *   ("workspace too small") on the host before any launch; nothing is written outside out and
+ *   the workspace.
+ * Argument errors (num_heads outside [1, MAXK_MAX_HEADS], a null pointer, k / D range, negative
+ *   sizes): MAXK_ERR_INVALID with a message naming the argument, before any launch.
+ * chunk_edges: tokens per wavefront work item, 0 = the forward's auto rule. */
+size_t maxk_spgemm_forward_heads_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                                                int32_t num_heads, int32_t chunk_edges);
+int maxk_spgemm_forward_heads(const int32_t *row_ptr, const int32_t *col_idx,
+                              const float *edge_val, const float *cbsr_val,
+                              const uint8_t *cbsr_idx, const float *row_div, float *out,
+                              int64_t num_rows, int64_t num_cols, int64_t num_e,
+                              int32_t dim_origin, int32_t dim_k, int32_t num_heads,
+                              int32_t chunk_edges, void *workspace, size_t workspace_bytes,
+                              void *stream);
+
+/* grad_edge[h, e] = ( sum_l cbsr_val[c,l] * grad_out[h, r, cbsr_idx[c,l]] ) / row_div[r]   for
+ * every head h: maxk_edge_weight_grad per head, the adjoint of maxk_spgemm_forward_heads in
+ * edge_val.  The reference has no counterpart.  Per row piece the H rows grad_out[h, r, :] are
+ * staged in LDS; per edge one record load, then one fma and one fixed-shape sum per head.
+ * Shapes, numerics and memory are maxk_edge_weight_grad's, per head (the same tree in the same
+ *   order: at num_heads == 1 the result equals maxk_edge_weight_grad's bitwise), except that a
+ *   table past 2^24 columns or 4 GiB of packed records is rejected with MAXK_ERR_INVALID.
+ *   num_e == 0 launches nothing and succeeds.  grad_edge [num_heads, num_e] is fully written.
+ * Argument errors as maxk_spgemm_forward_heads. */
+size_t maxk_edge_weight_grad_heads_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                  int64_t num_e, int32_t dim_origin,
+                                                  int32_t dim_k, int32_t num_heads,
+                                                  int32_t chunk_edges);
+int maxk_edge_weight_grad_heads(const int32_t *row_ptr, const int32_t *col_idx,
+                                const float *cbsr_val, const uint8_t *cbsr_idx,
+                                const float *grad_out, const float *row_div, float *grad_edge,
+                                int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                int32_t dim_origin, int32_t dim_k, int32_t num_heads,
+                                int32_t chunk_edges, void *workspace, size_t workspace_bytes,
+                                void *stream);
+
+/* ---------------------------------------------------------------------------
  * Edge softmax: the weights of a destination's incoming edges, normalised over its CSR row,
  * and their backward -- what produces the edge weights maxk_spgemm_forward takes and consumes
  * the gradient maxk_edge_weight_grad returns.  The reference has no counterpart.

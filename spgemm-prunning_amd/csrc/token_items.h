@@ -1,7 +1,7 @@
 // The token-stream work partition, stated once for every kernel that walks
 // a CSR or a CSC by items: the forward (spgemm_fwd.hip), the push and the csc sum
-// (sspmm_push.hip), the dense route's two walks (dense_route.hip) and the edge-weight gradient
-// (edge_grad.hip).
+// (sspmm_push.hip), the dense route's two walks (dense_route.hip), the edge-weight gradient
+// (edge_grad.hip) and the multi-head forms of the first and the last (spgemm_fwd_heads.hip).
 //
 // A pointer array ptr[0..n] is read as a stream of n row tokens and num_e edge tokens: row q's
 // token sits at q + ptr[q], edge e of row q at e + q + 1.  Item i is the tokens

@@ -47,6 +47,7 @@ __all__ = [
     "build_warp4_metadata", "warp4_to_indptr",
     "spgemm_forward", "sspmm_backward", "edge_weight_grad", "graph_only_mode", "DenseSpMMPlan",
     "edge_softmax", "edge_softmax_backward", "gat_edge_softmax", "gat_edge_softmax_backward",
+    "spgemm_forward_heads", "edge_weight_grad_heads", "MAX_HEADS", "heads_forward_route",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -330,6 +331,109 @@ def edge_weight_grad(indptr: torch.Tensor, indices: torch.Tensor, cbsr_val: torc
     _launch_ws(dev, "maxk_edge_weight_grad", "maxk_edge_weight_grad_workspace_size", shape,
                (_ptr(indptr), _ptr(indices), _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(grad_output),
                 _ptr(row_div), _ptr(out), *shape))
+    return out
+
+
+MAX_HEADS = 8  # MAXK_MAX_HEADS (maxk_hip.h)
+
+
+def _heads_operands(indptr, indices, cbsr_val, cbsr_idx, row_div, validate, D):
+    """The operand checks the two multi-head calls share; returns (num_rows, num_cols, k)."""
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (cbsr_val, "input_data", torch.float32),
+                     (cbsr_idx, "sparse_selector", torch.uint8)):
+        _need(t, n, dt)
+    if cbsr_val.dim() != 2 or cbsr_idx.shape != cbsr_val.shape:
+        raise RuntimeError("input_data and sparse_selector must have the same [V, k] shape")
+    num_cols, k = cbsr_val.shape
+    num_rows = indptr.numel() - 1
+    if row_div is not None:
+        _need(row_div, "row_div", torch.float32)
+        if row_div.numel() != num_rows:
+            raise RuntimeError("row_div must have num_rows entries")
+    _validate_call(validate, indptr, indices, num_cols, cbsr_idx, D)
+    return num_rows, num_cols, k
+
+
+def _heads_out(out, shape, dev, what):
+    if out is None:
+        return torch.empty(*shape, dtype=torch.float32, device=dev)
+    _need(out, "out", torch.float32)
+    if tuple(out.shape) != tuple(shape):
+        raise RuntimeError(f"out must be {what}")
+    return out
+
+
+def spgemm_forward_heads(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
+                         cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor, dim_origin: int,
+                         row_div: Optional[torch.Tensor] = None, chunk: int = 0,
+                         out: Optional[torch.Tensor] = None,
+                         validate: Optional[bool] = None) -> torch.Tensor:
+    """out[H, num_rows, D]: spgemm_forward for H sets of edge weights, values [H, E], over one
+    graph and one CBSR, with one record gather per edge serving all heads
+    (maxk_spgemm_forward_heads).  1 <= H <= MAX_HEADS; row_div is shared by the heads.  Head
+    h's slice equals, within the forward's bound, spgemm_forward(..., values[h], ...); bitwise
+    repeatable.  The same operand checks as spgemm_forward."""
+    D = int(dim_origin)
+    _need(values, "values", torch.float32)
+    num_rows, num_cols, k = _heads_operands(indptr, indices, cbsr_val, cbsr_idx, row_div,
+                                            validate, D)
+    E = indices.numel()
+    if values.dim() != 2 or values.shape[1] != E or not 1 <= values.shape[0] <= MAX_HEADS:
+        raise RuntimeError(f"values must be [H, num_e] with 1 <= H <= {MAX_HEADS}")
+    H = values.shape[0]
+    dev = cbsr_val.device
+    out = _heads_out(out, (H, num_rows, D), dev, "[H, num_rows, dim_origin]")
+    shape = (num_rows, num_cols, E, D, k, H, chunk)
+    _launch_ws(dev, "maxk_spgemm_forward_heads", "maxk_spgemm_forward_heads_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(cbsr_val), _ptr(cbsr_idx),
+                _ptr(row_div), _ptr(out), *shape))
+    return out
+
+
+HEADS_SPARSE_DEGREE = 128  # kFwdSparseDegree (cbsr_pack.h): below it a graph is "sparse"
+
+
+def heads_forward_route(num_rows: int, num_e: int) -> str:
+    """How a multi-head aggregation's forward runs (CSRGraph.aggregate_heads, maxk_spgemm_heads):
+    "heads", one spgemm_forward_heads call, on a sparse graph (average degree below
+    HEADS_SPARSE_DEGREE), where the record gathers are random memory lines and sharing them
+    pays -- ogbn-products-sized, k = 32: 0.84 (H = 4) and 0.81 (H = 8) of the H single-head
+    calls; "calls", H spgemm_forward calls into the slices of one output, on a dense one, whose
+    records stay in the caches -- Reddit-sized, k = 16: 1.00 and 0.99, inside the run-to-run
+    spread (profiles/r12/heads/).  The weight gradient takes
+    edge_weight_grad_heads everywhere (0.52 to 0.62).  MAXK_HEADS_FWD=heads|calls forces one."""
+    forced = os.environ.get("MAXK_HEADS_FWD", "")
+    if forced in ("heads", "calls"):
+        return forced
+    return "heads" if num_e < HEADS_SPARSE_DEGREE * num_rows else "calls"
+
+
+def edge_weight_grad_heads(indptr: torch.Tensor, indices: torch.Tensor, cbsr_val: torch.Tensor,
+                           cbsr_idx: torch.Tensor, grad_output: torch.Tensor,
+                           row_div: Optional[torch.Tensor] = None, chunk: int = 0,
+                           out: Optional[torch.Tensor] = None,
+                           validate: Optional[bool] = None) -> torch.Tensor:
+    """grad_edge[H, E]: edge_weight_grad for H gradients grad_output [H, num_rows, D] of
+    spgemm_forward_heads, with one record gather per edge serving all heads
+    (maxk_edge_weight_grad_heads).  Head h's slice is bitwise edge_weight_grad(...,
+    grad_output[h], ...)."""
+    _need(grad_output, "grad_output", torch.float32)
+    if grad_output.dim() != 3 or not 1 <= grad_output.shape[0] <= MAX_HEADS:
+        raise RuntimeError(f"grad_output must be [H, num_rows, dim_origin] with 1 <= H <= "
+                           f"{MAX_HEADS}")
+    H, _, D = grad_output.shape
+    num_rows, num_cols, k = _heads_operands(indptr, indices, cbsr_val, cbsr_idx, row_div,
+                                            validate, D)
+    if grad_output.shape[1] != num_rows:
+        raise RuntimeError("grad_output must be [H, num_rows, dim_origin]")
+    E = indices.numel()
+    dev = grad_output.device
+    out = _heads_out(out, (H, E), dev, "[H, num_e]")
+    shape = (num_rows, num_cols, E, D, k, H, chunk)
+    _launch_ws(dev, "maxk_edge_weight_grad_heads", "maxk_edge_weight_grad_heads_workspace_size",
+               shape, (_ptr(indptr), _ptr(indices), _ptr(cbsr_val), _ptr(cbsr_idx),
+                       _ptr(grad_output), _ptr(row_div), _ptr(out), *shape))
     return out
 
 

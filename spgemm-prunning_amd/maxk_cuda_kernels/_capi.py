@@ -47,6 +47,13 @@ SIGNATURES = {
     "maxk_edge_weight_grad_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
     "maxk_edge_weight_grad": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                              _i32, _i32, _i32, _p, _sz, _p]),
+    "maxk_spgemm_forward_heads_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "maxk_spgemm_forward_heads": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
+                                                 _i32, _i32, _i32, _i32, _p, _sz, _p]),
+    "maxk_edge_weight_grad_heads_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32,
+                                                         _i32]),
+    "maxk_edge_weight_grad_heads": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
+                                                   _i32, _i32, _i32, _i32, _p, _sz, _p]),
     "maxk_edge_softmax_workspace_size": (_sz, [_i64, _i64, _i64, _i32]),
     "maxk_edge_softmax": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _sz, _p]),
     "maxk_edge_softmax_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32]),

@@ -39,7 +39,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 import maxk_cuda_kernels as mk
-from maxk_spgemm_function import maxk_spgemm
+from maxk_spgemm_function import maxk_spgemm, maxk_spgemm_heads
 
 
 def _clamped(graph, name: str) -> torch.Tensor:
@@ -86,6 +86,12 @@ class CSRGraph:
         return maxk_spgemm(self.indices, self.values if values is None else values,
                            topk_values, topk_indices, None, 0, self.indptr, row_div,
                            dim_origin=dim)
+
+    def aggregate_heads(self, topk_values, topk_indices, dim: int, values, row_div=None):
+        """[H, V, dim]: aggregate() for the H weight sets values [H, E] (attention heads), one
+        record gather per edge serving all heads (maxk_spgemm_heads)."""
+        return maxk_spgemm_heads(self.indptr, self.indices, values, topk_values, topk_indices,
+                                 dim, row_div)
 
 
 class MaxK(Function):
@@ -382,6 +388,15 @@ def gat_edge_softmax(graph: CSRGraph, s_dst: torch.Tensor, s_src: torch.Tensor,
     return GATEdgeSoftmax.apply(graph.indptr, graph.indices, s_dst, s_src, negative_slope)
 
 
+def gat_edge_softmax_heads(graph: CSRGraph, s_dst: torch.Tensor, s_src: torch.Tensor,
+                           negative_slope: float = 0.2) -> torch.Tensor:
+    """alpha [H, E] float32 of H GAT heads from their scores s_dst [H, V], s_src [H, V]: the
+    single-head pass on each head's contiguous slice, stacked."""
+    s_dst, s_src = s_dst.contiguous(), s_src.contiguous()
+    return torch.stack([GATEdgeSoftmax.apply(graph.indptr, graph.indices, s_dst[h], s_src[h],
+                                             negative_slope) for h in range(s_dst.shape[0])])
+
+
 class MaxKGATConv(nn.Module):
     """Single-head GAT on MaxK features:
     rst[v] = sum_{u in N(v)} alpha_vu fc(x_sparse[u]) + b,
@@ -417,6 +432,53 @@ class MaxKGATConv(nn.Module):
         agg = graph.aggregate(topk_values, topk_indices, self.in_feats, values=alpha,
                               row_div=None)
         rst = linear(agg, self.fc)
+        if self.bias is not None:
+            rst = rst + self.bias
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst
+
+
+class MaxKMultiHeadGATConv(nn.Module):
+    """GAT with num_heads heads on MaxK features; returns [V, num_heads, out_feats], as the
+    usual multi-head GATConv does:
+    rst[v, h] = sum_{u in N(v)} alpha_hvu W_h x_sparse[u] + b_h,
+    alpha_hv. = softmax_u leaky_relu(attn_dst[h] . W_h x_sparse[v]
+                                     + attn_src[h] . W_h x_sparse[u]),
+    W_h = fc.weight[h * out_feats:(h + 1) * out_feats].  The scores of all heads come from one
+    [V, in] x [in, 2H] product, alpha [H, E] from the HIP softmax per head, and the aggregation
+    of all heads from one multi-head call on the CBSR (CSRGraph.aggregate_heads: one record
+    gather per edge whatever H), agg [H, V, in]; the Linear follows it as one bmm.  Gradients
+    reach fc.weight, both attention matrices, x_sparse through the scores and topk_values
+    through the aggregation."""
+
+    def __init__(self, in_feats: int, out_feats: int, num_heads: int,
+                 negative_slope: float = 0.2, bias: bool = True, activation=None):
+        super().__init__()
+        if not 1 <= int(num_heads) <= mk.MAX_HEADS:
+            raise ValueError(f"num_heads must be in [1, {mk.MAX_HEADS}], got {num_heads}")
+        self.in_feats, self.out_feats, self.num_heads = in_feats, out_feats, int(num_heads)
+        self.negative_slope = float(negative_slope)
+        self.fc = nn.Linear(in_feats, self.num_heads * out_feats, bias=False)
+        self.attn_src = nn.Parameter(torch.empty(self.num_heads, out_feats))
+        self.attn_dst = nn.Parameter(torch.empty(self.num_heads, out_feats))
+        self.bias = nn.Parameter(torch.zeros(self.num_heads, out_feats)) if bias else None
+        self.activation = activation
+        gain = nn.init.calculate_gain("relu")  # as the usual GATConv: Xavier-normal, ReLU gain
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn_src, gain=gain)
+        nn.init.xavier_normal_(self.attn_dst, gain=gain)
+
+    def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices):
+        H, O = self.num_heads, self.out_feats
+        W = self.fc.weight.view(H, O, self.in_feats)
+        # attn[h] . W_h x = x . (W_h^T attn[h]): every head's two scores from one product
+        v = torch.cat((torch.einsum("hoi,ho->ih", W, self.attn_dst),
+                       torch.einsum("hoi,ho->ih", W, self.attn_src)), 1)  # [in, 2H]
+        s = (x_sparse @ v).t().contiguous()                               # [2H, V]
+        alpha = gat_edge_softmax_heads(graph, s[:H], s[H:], self.negative_slope)
+        agg = graph.aggregate_heads(topk_values, topk_indices, self.in_feats, alpha)
+        rst = torch.bmm(agg, W.transpose(1, 2)).transpose(0, 1)          # [V, H, out]
         if self.bias is not None:
             rst = rst + self.bias
         if self.activation is not None:

@@ -306,6 +306,80 @@ def maxk_spgemm(graph_indices, graph_values, a3, a4, *rest, **kw):
     return MaxKSpGEMMFunction.apply(graph_indices, graph_values, a3, a4, *args)
 
 
+class MaxKSpGEMMHeadsFunction(Function):
+    """H aggregations over one graph and one CBSR that differ in their edge weights (attention
+    heads): apply(graph_indptr, graph_indices, graph_values [H, E], topk_values [V, k],
+    topk_indices [V, k], dim_origin, degrees) -> [H, V, dim_origin].
+
+    The forward and the weight gradient are the multi-head kernels (one record gather per edge
+    for all heads: maxk_cuda_kernels.spgemm_forward_heads / edge_weight_grad_heads); on a dense
+    graph, where the multi-head forward measured no faster, the forward is H single-head calls
+    into the slices of the output instead (maxk_cuda_kernels.heads_forward_route).  The
+    feature gradient is the sum over the heads, in head order, of the existing sspmm_backward
+    on (graph_values[h], grad_output[h]) in the graph-only mode the single-head function takes
+    with differentiable weights -- H launches of an existing kernel; a fused multi-head
+    feature backward is the follow-up."""
+
+    @staticmethod
+    def forward(ctx, graph_indptr, graph_indices, graph_values, topk_values, topk_indices,
+                dim_origin, degrees):
+        _require_kernels()
+        indptr, indices = _i32(graph_indptr), _i32(graph_indices)
+        vals = _f32_act(topk_values)
+        sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
+        sel = sel.contiguous()
+        w = _f32_act(graph_values)  # attention weights change every step: never cached
+        row_div = _f32(degrees)
+        D = int(dim_origin)
+        V, k = vals.shape
+        num_rows = indptr.numel() - 1
+        if maxk_cuda_kernels.heads_forward_route(num_rows, indices.numel()) == "heads":
+            out = maxk_cuda_kernels.spgemm_forward_heads(indptr, indices, w, vals, sel, D,
+                                                         row_div=row_div)
+        else:  # a dense graph: the multi-head kernel measured no faster there (DESIGN.md 5.7)
+            if w.dim() != 2 or not 1 <= w.shape[0] <= maxk_cuda_kernels.MAX_HEADS:
+                raise RuntimeError("graph_values must be [H, num_e] with 1 <= H <= "
+                                   f"{maxk_cuda_kernels.MAX_HEADS}")
+            out = torch.empty(w.shape[0], num_rows, D, dtype=torch.float32, device=vals.device)
+            for h in range(w.shape[0]):
+                maxk_cuda_kernels.spgemm_forward(indptr, indices, w[h], vals, sel, D,
+                                                 row_div=row_div, out=out[h])
+        ctx.bwd_mode = maxk_cuda_kernels.graph_only_mode(k, indices.numel(), V)
+        ctx.has_div = row_div is not None
+        ctx.save_for_backward(indptr, indices, w, vals, sel,
+                              row_div if row_div is not None else torch.empty(0))
+        ctx.w_dtype = graph_values.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        indptr, indices, w, vals, sel, row_div = ctx.saved_tensors
+        row_div = row_div if ctx.has_div else None
+        g = grad_output.contiguous()
+        if g.dtype != torch.float32:
+            g = g.float()
+        grad_w = grad_tv = None
+        if ctx.needs_input_grad[2]:
+            grad_w = maxk_cuda_kernels.edge_weight_grad_heads(indptr, indices, vals, sel, g,
+                                                              row_div=row_div).to(ctx.w_dtype)
+        if ctx.needs_input_grad[3]:
+            for h in range(w.shape[0]):  # accumulated in head order
+                part = maxk_cuda_kernels.sspmm_backward(indptr, indices, w[h], g[h], sel,
+                                                        row_div=row_div, mode=ctx.bwd_mode)
+                grad_tv = part if grad_tv is None else grad_tv.add_(part)
+        return None, None, grad_w, grad_tv, None, None, None
+
+
+def maxk_spgemm_heads(graph_indptr, graph_indices, graph_values, topk_values, topk_indices,
+                      dim_origin, degrees=None):
+    """[H, V, dim_origin] = (A_h . scatter(topk)) / degrees for the H weight sets
+    graph_values [H, E] of one CSR graph; gradients for graph_values and topk_values
+    (MaxKSpGEMMHeadsFunction)."""
+    _require_kernels()
+    return MaxKSpGEMMHeadsFunction.apply(graph_indptr, graph_indices, graph_values, topk_values,
+                                         topk_indices, dim_origin, degrees)
+
+
 class MaxKSpmmWrapper:
     """Holds the warp4 metadata of one graph (maxk_spgemm_function.py:214-267)."""
 
