@@ -387,6 +387,54 @@ int maxk_edge_selectors(const int32_t *col_idx, const uint8_t *cbsr_idx, int64_t
  * CU and walked grid-stride, so num_e * k one-byte words past 2^32 still launch. */
 int64_t maxk_edge_selectors_blocks(int64_t n_words);
 
+/* ---------------------------------------------------------------------------
+ * The csc backward for H = num_heads heads (the multi-head layout above: edge_val f32
+ * [num_heads, num_e], grad_out f32 [num_heads, num_rows, dim_origin], one row_div), summed over
+ * the heads:
+ *   grad_cbsr[c,l] = sum_h sum_{e=(r->c)} edge_val[h,e] * grad_out[h, r, cbsr_idx[c,l]] / row_div[r]
+ * the adjoint of maxk_spgemm_forward_heads in cbsr_val; what H maxk_sspmm_backward_csc calls and
+ * H - 1 additions give.  The reference has no counterpart.  Phase 1 sums the heads per edge
+ * before it stores (per row piece the H rows grad_out[h, r, :] / row_div[r] are staged in LDS;
+ * per edge one column load, one selector gather, H weights, and one contribution row
+ * T[e, l] = sum_h edge_val[h,e] * g_h[cbsr_idx[c,l]], formed in head order with one fma per
+ * further head); phase 2 and the fix-up are maxk_sspmm_backward_csc's, over the same workspace
+ * layout.  col_ptr / csc_eid: the graph's maxk_transpose_plan.
+ * Shapes: any 1 <= dim_k <= dim_origin <= 256 (dim_k % 4 != 0, odd dim_origin, dim_k > 64).
+ *   There is no edge_sel, bsort, pull or dense form; a table of 2^24 columns or more is rejected
+ *   with MAXK_ERR_INVALID.  num_e == 0 writes zeros to all of grad_cbsr and succeeds; num_cols
+ *   == 0 launches nothing.
+ * Numerics, in the words of the top comment: every element is within (n + 8) * 2^-24 *
+ *   sum|terms| of exact arithmetic (plus the 2^-149 floor), n = num_heads times the number of
+ *   edges into column c and sum|terms| over every head's terms.  A slot without addends (a
+ *   column no edge reads, a selector >= dim_origin) is exactly 0; repeated selectors each
+ *   receive the same sum.  Inf and NaN in grad_out propagate as the IEEE sum of the selected
+ *   terms; a NaN in a column of grad_out the destination does not select, or in a row without
+ *   an edge to it, reaches nothing.  Non-finite weights and row_div are outside the contract.
+ *   The sum order is fixed by the graph, chunk_edges, dim_k and num_heads: bitwise repeatable,
+ *   and bitwise equivariant under a power-of-two scale of grad_out or of the weights away from
+ *   overflow and underflow.  At num_heads == 1 the result equals maxk_sspmm_backward_csc's
+ *   bitwise for the same chunk_edges (each T element is the same single product, phase 2 the
+ *   same code).
+ * Memory, as the top comment: the workspace is exactly the queried size -- what
+ *   maxk_sspmm_backward_csc_workspace_size returns for the same graph, dim_k and chunk_edges --
+ *   256-B aligned, and may hold anything; a shorter one is rejected ("workspace too small") on
+ *   the host before any launch; grad_cbsr [num_cols, dim_k] is fully written; inputs are never
+ *   written; nothing else is touched.  No atomics.
+ * Argument errors (num_heads outside [1, MAXK_MAX_HEADS], a null pointer, k / D range, negative
+ *   sizes): MAXK_ERR_INVALID with a message naming the argument, before any launch.
+ * chunk_edges: tokens per wavefront work item of both phases, 0 = the csc backward's auto rule.
+ * ------------------------------------------------------------------------- */
+size_t maxk_sspmm_backward_heads_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                                                int32_t num_heads, int32_t chunk_edges);
+int maxk_sspmm_backward_heads(const int32_t *row_ptr, const int32_t *col_idx,
+                              const float *edge_val, const float *grad_out, const float *row_div,
+                              const uint8_t *cbsr_idx, const int32_t *col_ptr,
+                              const int32_t *csc_eid, float *grad_cbsr, int64_t num_rows,
+                              int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                              int32_t num_heads, int32_t chunk_edges, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
 /* Transpose plan of a CSR graph (once per graph): col_ptr[num_cols+1] of the
  * CSC and csc_eid[num_e] = the CSR edge id held by CSC slot t (stable in CSR order).
  * Replaces the CSC side files of generate_meta_csc.py:14-93 /

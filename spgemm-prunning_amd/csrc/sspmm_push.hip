@@ -316,6 +316,285 @@ __global__ __launch_bounds__(kBlock, MAXK_BWD_WAVES) void sspmm_bwd_kernel(
     }
 }
 
+// ---- H heads (maxk_sspmm_backward_heads): edge_val [H, num_e], grad [H, num_rows, D] --------
+// The kStore phase 1 with the heads summed per edge before anything is stored,
+//   T[e, l] = sum_h w[h, e] * G[h, r, sel[c, l]] / row_div[r]     (c = col_idx[e], e in row r),
+// so an edge costs one column load, one selector gather and one contribution row whatever H;
+// phase 2 (csc_sum_kernel) then runs as for one head.  Per row piece the H rows G[h, r, :] /
+// row_div[r] are staged side by side in the wave's LDS (g_lds[h * DS + j], DS = heads_stride(D):
+// H * DS floats per wave, 8.3 KB at H = 8, D = 256; the pad columns [D, DS) hold zeros).  A
+// selector byte >= D is clamped to the last pad column (`trash`): with rows at a stride below
+// 256 it would otherwise read the next head's row.  Per edge and l the sum is formed in head
+// order, x = w[0] * g_0[s], then x = fma(w[h], g_h[s], x): at H == 1 the one product the
+// single-head kernel stores.
+// The weights of a batch, U * H per lane, are loaded with the batch's selectors and held in
+// registers (w[U][HB], HB = 4 or 8 >= H: the loops over heads are unrolled to HB under
+// wave-uniform h < H tests, so no array is indexed by a run-time value), which keeps the order
+// [columns of batch i+1] [selectors and weights of batch i] [stores of batch i-1] [wait]: the
+// stores in flight are younger than every load being waited for, as in push_edges.
+
+// LDS row stride of one head: D rounded up to 4 floats plus 4 zeroed pad floats (16-B rows).
+__host__ __device__ inline int heads_stride(int D) { return (D + 3) / 4 * 4 + 4; }
+
+// x[i] (+)= w * g[s_i] for the four selector bytes of sv, each clamped to the trash column
+template <bool FIRST>
+__device__ __forceinline__ void heads_term4(float (&x)[4], float w, const float *g, uint32_t sv,
+                                            uint32_t trash) {
+    const uint32_t s[4] = {sv & 255u, (sv >> 8) & 255u, (sv >> 16) & 255u, sv >> 24};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float gv = g[s[i] < trash ? s[i] : trash];
+        x[i] = FIRST ? w * gv : __builtin_fmaf(w, gv, x[i]);
+    }
+}
+
+// k % 4 == 0: push_x4 for H heads (LR = pow2ceil(k/4) lanes per edge, four l per lane, one u32
+// selector load and one 16-B store per edge and lane).  Columns, weights and T rows go through
+// buffer descriptors over the segment [sb, se): past se the loads return 0 (column 0, weight
+// 0) and the stores are dropped, as are those of the idle lanes q >= k/4.
+template <int LR, int U, int HB>
+__device__ __forceinline__ void push_heads_x4(const float *g_lds, int DS,
+                                              const int32_t *__restrict__ col_idx,
+                                              const float *__restrict__ edge_val, int64_t num_e,
+                                              int H, const uint8_t *__restrict__ cbsr_idx,
+                                              float *__restrict__ T, int sb, int se, int k,
+                                              int lane) {
+    constexpr int G = kWave / LR;
+    constexpr int GU = G * U;
+    const int grp = lane / LR;
+    const int q = lane % LR;
+    const int k4 = k >> 2;
+    const int n = se - sb;  // wave-uniform, <= chunk
+    const uint32_t trash = (uint32_t)DS - 1u;
+    const auto crs = wave_buffer(col_idx + sb, (uint32_t)n * 4u);
+    __amdgpu_buffer_rsrc_t vrs[HB];
+#pragma unroll
+    for (int h = 0; h < HB; ++h)
+        vrs[h] = wave_buffer(edge_val + (int64_t)(h < H ? h : 0) * num_e + sb, (uint32_t)n * 4u);
+    const auto srs = wave_buffer(cbsr_idx, 0xffffffffu);  // offsets < num_cols * k < 2^31
+    const auto trs = wave_buffer(T + (size_t)(uint32_t)sb * k, (uint32_t)n * k * 4u);
+    const uint32_t qsel = 4u * (uint32_t)(q < k4 ? q : k4 - 1);
+    const uint32_t qst = q < k4 ? 16u * q : 0x80000000u;  // store offset term; past the end if idle
+    const uint32_t kb = 4u * (uint32_t)k;                    // T row bytes
+    int c[U];
+    {
+        const int lo = grp * 4;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            c[u] = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, lo + u * G * 4, 0, 0);
+    }
+    u32x4 xp[U];
+    uint32_t sto = 0;  // T byte offset of the pending batch's step 0 for this lane
+    bool pending = false;
+    for (int base = 0;; base += GU) {  // base: edge offset inside the segment
+        const bool has_next = base + GU < n;  // wave-uniform
+        int cn[U];
+        if (has_next) {
+            const int lo = (base + GU + grp) * 4;
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                cn[u] = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, lo + u * G * 4, 0, 0);
+        }
+        uint32_t sv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            sv[u] = __builtin_amdgcn_raw_buffer_load_b32(
+                srs, (int)(__umul24((uint32_t)c[u], (uint32_t)k) + qsel), 0, 0);
+        float w[U][HB];
+        {
+            const int lo = (base + grp) * 4;
+#pragma unroll
+            for (int h = 0; h < HB; ++h) {
+                if (h < H) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        w[u][h] = __uint_as_float(
+                            __builtin_amdgcn_raw_buffer_load_b32(vrs[h], lo + u * G * 4, 0, 0));
+                }
+            }
+        }
+        if (pending) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                __builtin_amdgcn_raw_buffer_store_b128(xp[u], trs, (int)(sto + u * G * kb), 0,
+                                                       MAXK_T_AUX);
+        }
+        float x[U][4];
+#pragma unroll
+        for (int u = 0; u < U; ++u) heads_term4<true>(x[u], w[u][0], g_lds, sv[u], trash);
+#pragma unroll
+        for (int h = 1; h < HB; ++h) {
+            if (h < H) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    heads_term4<false>(x[u], w[u][h], g_lds + h * DS, sv[u], trash);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            xp[u].x = __float_as_uint(x[u][0]);
+            xp[u].y = __float_as_uint(x[u][1]);
+            xp[u].z = __float_as_uint(x[u][2]);
+            xp[u].w = __float_as_uint(x[u][3]);
+        }
+        sto = (uint32_t)(base + grp) * kb + qst;
+        pending = true;
+        if (!has_next) break;
+#pragma unroll
+        for (int u = 0; u < U; ++u) c[u] = cn[u];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        __builtin_amdgcn_raw_buffer_store_b128(xp[u], trs, (int)(sto + u * G * kb), 0, MAXK_T_AUX);
+}
+
+// Any k: KG = pow2ceil(k) lanes per edge (<= 64), one l per lane and pass, passes over l for
+// k > 64.  All loads unconditional with clamped addresses; a masked lane (past se, or l >= k)
+// stores to the dummy row T[num_e]; the stores of a pass are issued after the selector loads of
+// the next one.
+template <int KG, int U, int HB>
+__device__ __forceinline__ void push_heads_scalar(const float *g_lds, int DS,
+                                                  const int32_t *__restrict__ col_idx,
+                                                  const float *__restrict__ edge_val,
+                                                  int64_t num_e, int H,
+                                                  const uint8_t *__restrict__ cbsr_idx,
+                                                  float *__restrict__ T, int sb, int se, int k,
+                                                  int lane) {
+    constexpr int G = kWave / KG;
+    constexpr int GU = G * U;
+    const int grp = lane / KG;
+    const int l0 = lane % KG;
+    const int last = se - 1;
+    const int dummy = (int)num_e;
+    const int trash = DS - 1;
+    int c[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int e = sb + u * G + grp;
+        c[u] = col_idx[e < se ? e : last];
+    }
+    float xp[U] = {};
+    int rp[U];   // T row of each pending store (dummy for masked lanes)
+    int lp = 0;  // ... and its column
+    bool pending = false;
+    for (int base = sb;; base += GU) {
+        const bool has_next = base + GU < se;  // wave-uniform
+        int cn[U];
+        if (has_next) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int e = base + GU + u * G + grp;
+                cn[u] = col_idx[e < se ? e : last];
+            }
+        }
+        float w[U][HB];
+#pragma unroll
+        for (int h = 0; h < HB; ++h) {
+            if (h < H) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int e = base + u * G + grp;
+                    w[u][h] = edge_val[(int64_t)h * num_e + (e < se ? e : last)];
+                }
+            }
+        }
+        for (int lb = 0; lb < k; lb += KG) {  // one pass unless k > 64
+            const int l = lb + l0;
+            const bool lok = l < k;
+            const int lc = lok ? l : k - 1;
+            int s[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) s[u] = cbsr_idx[c[u] * k + lc];
+            if (pending) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) T[(size_t)(uint32_t)rp[u] * k + lp] = xp[u];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                s[u] = s[u] < trash ? s[u] : trash;
+                xp[u] = w[u][0] * g_lds[s[u]];
+            }
+#pragma unroll
+            for (int h = 1; h < HB; ++h) {
+                if (h < H) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        xp[u] = __builtin_fmaf(w[u][h], g_lds[h * DS + s[u]], xp[u]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int e = base + u * G + grp;
+                rp[u] = (e < se && lok) ? e : dummy;
+            }
+            lp = lc;
+            pending = true;
+        }
+        if (!has_next) break;
+#pragma unroll
+        for (int u = 0; u < U; ++u) c[u] = cn[u];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) T[(size_t)(uint32_t)rp[u] * k + lp] = xp[u];
+}
+
+// LG: lanes per edge (X4: pow2ceil(k/4), else pow2ceil(k)); HB: 4 or 8, >= H.
+template <int LG, int U, int HB, bool X4>
+__global__ __launch_bounds__(kBlock, MAXK_BWD_WAVES) void sspmm_bwd_heads_kernel(
+    const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
+    const float *__restrict__ edge_val, const float *__restrict__ grad,
+    const float *__restrict__ row_div, const uint8_t *__restrict__ cbsr_idx,
+    float *__restrict__ T, int num_rows, int64_t num_e, int D, int DS, int k, int chunk,
+    int n_items, int H, int vec) {
+    extern __shared__ __attribute__((aligned(16))) float g_heads[];  // [kWavesPerBlock][H * DS]
+    const int wid = threadIdx.x / kWave;
+    const int lane = lane_id();
+    const int blk = MAXK_P1_XCD ? xcd_contiguous_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int item = blk * kWavesPerBlock + wid;
+    if (item >= n_items) return;  // whole wave; no workgroup barrier below
+    float *g_lds = g_heads + (size_t)wid * H * DS;
+    // the pad columns [D, DS) of every head's row are never staged over: zeroed once
+    for (int h = 0; h < H; ++h)
+        if (lane < DS - D) g_lds[h * DS + D + lane] = 0.f;
+
+    const ItemRange it = item_range(row_ptr, num_rows, num_e, item, chunk);
+    // rows q = r - 1 (continuation), r, r + 1, ...: each one's piece under CutAtEnd, row_ptr of
+    // 64 consecutive rows one per lane, as in sspmm_bwd_kernel
+    int q = it.r > 0 ? it.r - 1 : 0;
+    PtrWindow win{row_ptr, num_rows, 0, 0};
+    win.load(q, lane);
+    for (; q < num_rows; ++q) {
+        win.slide(q, lane);
+        const int rb = win.begin(q);
+        const int re = win.end(q);
+        if (!row_owned(it.d1, q, rb)) break;
+        const RowPiece p = any_piece(CutAtEnd{}, it.d0, it.d1, q, rb, re);
+        if (p.sb >= p.se) continue;
+        const float div = row_div ? row_div[q] : 1.f;
+        wave_lds_fence();  // the previous piece's reads of g_lds are done
+        for (int h = 0; h < H; ++h) {
+            const float *gr = grad + ((int64_t)h * num_rows + q) * D;
+            float *gl = g_lds + h * DS;
+            if (vec) {
+                for (int j = lane * 4; j < D; j += kWave * 4) {
+                    float4 v = *reinterpret_cast<const float4 *>(&gr[j]);
+                    if (row_div) v = make_float4(v.x / div, v.y / div, v.z / div, v.w / div);
+                    *reinterpret_cast<float4 *>(&gl[j]) = v;
+                }
+            } else {
+                for (int j = lane; j < D; j += kWave) gl[j] = row_div ? gr[j] / div : gr[j];
+            }
+        }
+        wave_lds_fence();
+        if constexpr (X4)
+            push_heads_x4<LG, U, HB>(g_lds, DS, col_idx, edge_val, num_e, H, cbsr_idx, T,
+                                     (int)p.sb, (int)p.se, k, lane);
+        else
+            push_heads_scalar<LG, U, HB>(g_lds, DS, col_idx, edge_val, num_e, H, cbsr_idx, T,
+                                         (int)p.sb, (int)p.se, k, lane);
+    }
+}
+
 // ---- phase 2: grad_cbsr[c, :] = sum over the CSC slots t of c of T[eid[t], :] -------
 
 // Sum the contribution rows T[eid[t]] (k floats each) for t in [tb, te) into
@@ -567,6 +846,41 @@ int launch_push(hipStream_t s, const int32_t *row_ptr, const int32_t *col_idx,
     return MAXK_OK;
 }
 
+// Phase 1 for H heads, at depth kHeadsDepth = 4 on every graph: a lane holds U * HB weights, and
+// at depth 8 with HB = 8 the kernel needs 187 VGPRs (two waves per SIMD, against four at depth
+// 4) -- Reddit-sized k = 16, the workload whose degree would pick 8 (pick_depth): H = 8 7.04 ms
+// at depth 8, 0.192 of the H calls of that run, 5.60 ms and 0.159 at depth 4; H = 4 5.18 and
+// 5.25 ms, 0.286 and 0.289 (profiles/r13/heads_bwd/bench_depth_by_degree.json, bench.json).
+constexpr int kHeadsDepth = 4;
+int launch_push_heads(hipStream_t s, const int32_t *row_ptr, const int32_t *col_idx,
+                      const float *edge_val, const float *grad, const float *row_div,
+                      const uint8_t *cbsr_idx, float *T, int nr, int64_t num_e, int D, int k,
+                      int H, int chunk) {
+    const int n_items = token_items(nr, num_e, chunk);
+    const int64_t blocks = ceil_div(n_items, kWavesPerBlock);
+    const dim3 grid((unsigned)(MAXK_P1_XCD ? xcd_grid(blocks) : blocks));
+    const int DS = heads_stride(D);
+    const size_t lds = (size_t)kWavesPerBlock * H * DS * sizeof(float);
+    const int vec = D % 4 == 0 && ((uintptr_t)grad & 15) == 0;
+    const bool x4 = k % 4 == 0;
+    const int lg = lanes_per_edge(x4 ? k / 4 : k);
+    const bool ok = with_lanes(lg, [&](auto lg_c) {
+        with_const<4, 8>(H <= 4 ? 4 : 8, [&](auto hb_c) {
+            with_const<0, 1>(x4, [&](auto x4_c) {
+                constexpr int LG = decltype(lg_c)::value, HB = decltype(hb_c)::value;
+                constexpr bool X4 = decltype(x4_c)::value;
+                hipLaunchKernelGGL((sspmm_bwd_heads_kernel<LG, kHeadsDepth, HB, X4>), grid,
+                                   dim3(kBlock), lds, s, row_ptr, col_idx, edge_val, grad,
+                                   row_div, cbsr_idx, T, nr, num_e, D, DS, k, chunk, n_items, H,
+                                   vec);
+            });
+        });
+    });
+    if (!ok) return bad_lanes(lg);
+    MAXK_LAUNCHED("sspmm_bwd_heads_kernel");
+    return MAXK_OK;
+}
+
 bool vec_sum(int k) { return k >= 4 && (k & (k - 1)) == 0; }
 
 struct CscLayout {
@@ -632,37 +946,14 @@ extern "C" size_t maxk_sspmm_backward_csc_workspace_size(int64_t num_rows, int64
 
 namespace maxk {
 namespace {
-// edge_sel (k % 4 == 0): phase 1 reads each edge's selectors from this per-edge stream instead
-// of gathering them from cbsr_idx (push_x4, ES).
-int csc_impl(const int32_t *row_ptr, const int32_t *col_idx, const float *edge_val,
-             const float *grad_out, const float *row_div, const uint8_t *cbsr_idx,
-             const uint8_t *edge_sel, const int32_t *col_ptr, const int32_t *csc_eid,
-             float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e,
-             int32_t dim_origin, int32_t dim_k, int32_t chunk_edges, void *workspace,
-             size_t workspace_bytes, void *stream) {
-    if (int rc = check_common(num_rows, num_cols, num_e, dim_origin, dim_k, chunk_edges)) return rc;
-    hipStream_t s = as_stream(stream);
-    if (num_cols == 0) return MAXK_OK;
-    MAXK_REQUIRE(grad_cbsr && col_ptr, "grad_cbsr/col_ptr must not be NULL");
-    MAXK_REQUIRE(num_e == 0 || (row_ptr && col_idx && edge_val && grad_out &&
-                                (cbsr_idx || edge_sel) && csc_eid),
-                 "CSR/grad/selector/transpose pointers must not be NULL");
-    const CscLayout L = csc_layout(num_cols, num_e, dim_k, chunk_edges);
-    MAXK_REQUIRE(workspace && workspace_bytes >= L.total,
-                 "workspace too small: need %zu bytes, got %zu", L.total, workspace_bytes);
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *T = reinterpret_cast<float *>(ws);
+// Phase 2 and the fix-up over the csc_layout workspace `ws`, whose contribution rows T phase 1
+// has written: the launch both the single-head csc backward and the multi-head one end with.
+int launch_csc_sum(hipStream_t s, const CscLayout &L, const int32_t *col_ptr,
+                   const int32_t *csc_eid, char *ws, float *grad_cbsr, int64_t num_cols,
+                   int64_t num_e, int k) {
+    const float *T = reinterpret_cast<const float *>(ws);
     float *slab = reinterpret_cast<float *>(ws + L.slab_off);
     int32_t *slab_row = reinterpret_cast<int32_t *>(ws + L.row_off);
-    const int k = dim_k;
-    if (num_e > 0 && num_rows > 0) {
-        if (int rc = launch_push<kStore>(s, row_ptr, col_idx, edge_val, grad_out, row_div,
-                                         cbsr_idx, T, (int)num_rows, num_cols, num_e,
-                                         dim_origin, k,
-                                         bwd_chunk(num_rows, num_e, chunk_edges, MAXK_P1_ITEMS),
-                                         edge_sel))
-            return rc;
-    }
     const int64_t blocks = ceil_div(L.n_items, kWavesPerBlock);
     const dim3 grid((unsigned)(MAXK_XCD_SUM ? xcd_grid(blocks) : blocks));
     const int nc = (int)num_cols;
@@ -710,6 +1001,38 @@ int csc_impl(const int32_t *row_ptr, const int32_t *col_idx, const float *edge_v
     if (!ok) return bad_lanes(kg);
     MAXK_LAUNCHED("csc_sum_kernel");
     return launch_slab_fixup<1>(slab, slab_row, grad_cbsr, k, L.n_items, s);
+}
+
+// edge_sel (k % 4 == 0): phase 1 reads each edge's selectors from this per-edge stream instead
+// of gathering them from cbsr_idx (push_x4, ES).
+int csc_impl(const int32_t *row_ptr, const int32_t *col_idx, const float *edge_val,
+             const float *grad_out, const float *row_div, const uint8_t *cbsr_idx,
+             const uint8_t *edge_sel, const int32_t *col_ptr, const int32_t *csc_eid,
+             float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e,
+             int32_t dim_origin, int32_t dim_k, int32_t chunk_edges, void *workspace,
+             size_t workspace_bytes, void *stream) {
+    if (int rc = check_common(num_rows, num_cols, num_e, dim_origin, dim_k, chunk_edges)) return rc;
+    hipStream_t s = as_stream(stream);
+    if (num_cols == 0) return MAXK_OK;
+    MAXK_REQUIRE(grad_cbsr && col_ptr, "grad_cbsr/col_ptr must not be NULL");
+    MAXK_REQUIRE(num_e == 0 || (row_ptr && col_idx && edge_val && grad_out &&
+                                (cbsr_idx || edge_sel) && csc_eid),
+                 "CSR/grad/selector/transpose pointers must not be NULL");
+    const CscLayout L = csc_layout(num_cols, num_e, dim_k, chunk_edges);
+    MAXK_REQUIRE(workspace && workspace_bytes >= L.total,
+                 "workspace too small: need %zu bytes, got %zu", L.total, workspace_bytes);
+    char *ws = reinterpret_cast<char *>(workspace);
+    float *T = reinterpret_cast<float *>(ws);
+    const int k = dim_k;
+    if (num_e > 0 && num_rows > 0) {
+        if (int rc = launch_push<kStore>(s, row_ptr, col_idx, edge_val, grad_out, row_div,
+                                         cbsr_idx, T, (int)num_rows, num_cols, num_e,
+                                         dim_origin, k,
+                                         bwd_chunk(num_rows, num_e, chunk_edges, MAXK_P1_ITEMS),
+                                         edge_sel))
+            return rc;
+    }
+    return launch_csc_sum(s, L, col_ptr, csc_eid, ws, grad_cbsr, num_cols, num_e, k);
 }
 
 // edge_sel[e * k + l] = cbsr_idx[col_idx[e] * k + l]: wb = 16, 4 or 1 bytes per thread (the
@@ -769,6 +1092,52 @@ extern "C" int maxk_sspmm_backward_csc_sel(const int32_t *row_ptr, const int32_t
     return csc_impl(row_ptr, col_idx, edge_val, grad_out, row_div, nullptr, edge_sel, col_ptr,
                     csc_eid, grad_cbsr, num_rows, num_cols, num_e, dim_origin, dim_k, chunk_edges,
                     workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t maxk_sspmm_backward_heads_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                           int64_t num_e, int32_t dim_origin,
+                                                           int32_t dim_k, int32_t num_heads,
+                                                           int32_t chunk_edges) {
+    if (num_heads < 1 || num_heads > MAXK_MAX_HEADS) return 0;
+    return maxk_sspmm_backward_csc_workspace_size(num_rows, num_cols, num_e, dim_origin, dim_k,
+                                                  chunk_edges);
+}
+
+extern "C" int maxk_sspmm_backward_heads(const int32_t *row_ptr, const int32_t *col_idx,
+                                         const float *edge_val, const float *grad_out,
+                                         const float *row_div, const uint8_t *cbsr_idx,
+                                         const int32_t *col_ptr, const int32_t *csc_eid,
+                                         float *grad_cbsr, int64_t num_rows, int64_t num_cols,
+                                         int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                                         int32_t num_heads, int32_t chunk_edges, void *workspace,
+                                         size_t workspace_bytes, void *stream) {
+    clear_error();
+    if (int rc = check_common(num_rows, num_cols, num_e, dim_origin, dim_k, chunk_edges)) return rc;
+    MAXK_REQUIRE(num_heads >= 1 && num_heads <= MAXK_MAX_HEADS,
+                 "num_heads must be in [1,%d], got %d", MAXK_MAX_HEADS, num_heads);
+    MAXK_REQUIRE(num_cols < (1 << 24), "num_cols: the multi-head feature backward takes tables "
+                 "below 2^24 columns (%lld columns)", (long long)num_cols);
+    if (num_cols == 0) return MAXK_OK;
+    MAXK_REQUIRE(grad_cbsr && col_ptr, "grad_cbsr/col_ptr must not be NULL");
+    MAXK_REQUIRE(num_e == 0 || (row_ptr && col_idx && edge_val && grad_out && cbsr_idx && csc_eid),
+                 "CSR/grad/selector/transpose pointers must not be NULL");
+    const CscLayout L = csc_layout(num_cols, num_e, dim_k, chunk_edges);
+    MAXK_REQUIRE(workspace && workspace_bytes >= L.total,
+                 "workspace too small: need %zu bytes, got %zu", L.total, workspace_bytes);
+    MAXK_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-B aligned");
+    MAXK_REQUIRE(((uintptr_t)edge_val & 3) == 0 && ((uintptr_t)grad_out & 3) == 0 &&
+                     ((uintptr_t)grad_cbsr & 3) == 0,
+                 "float buffers must be 4-B aligned");
+    hipStream_t s = as_stream(stream);
+    char *ws = reinterpret_cast<char *>(workspace);
+    if (num_e > 0 && num_rows > 0) {
+        if (int rc = launch_push_heads(s, row_ptr, col_idx, edge_val, grad_out, row_div, cbsr_idx,
+                                       reinterpret_cast<float *>(ws), (int)num_rows, num_e,
+                                       dim_origin, dim_k, num_heads,
+                                       bwd_chunk(num_rows, num_e, chunk_edges, MAXK_P1_ITEMS)))
+            return rc;
+    }
+    return launch_csc_sum(s, L, col_ptr, csc_eid, ws, grad_cbsr, num_cols, num_e, dim_k);
 }
 
 // edge_sel_kernel's grid: one thread per word up to 64 workgroups per CU, then grid-stride

@@ -48,6 +48,7 @@ __all__ = [
     "spgemm_forward", "sspmm_backward", "edge_weight_grad", "graph_only_mode", "DenseSpMMPlan",
     "edge_softmax", "edge_softmax_backward", "gat_edge_softmax", "gat_edge_softmax_backward",
     "spgemm_forward_heads", "edge_weight_grad_heads", "MAX_HEADS", "heads_forward_route",
+    "sspmm_backward_heads", "heads_backward_route",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -1175,6 +1176,80 @@ def _bwd_csc(indptr, indices, values, G, row_div, sel, edge_sel, out, shape, chu
 
 _BWD = {"dense": _bwd_dense, "hybrid": _bwd_hybrid, "pull": _bwd_pull, "bsort": _bwd_bsort,
         "atomic": _bwd_atomic, "csc": _bwd_csc}
+
+
+def sspmm_backward_heads(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
+                         grad_output: torch.Tensor, cbsr_idx: torch.Tensor,
+                         row_div: Optional[torch.Tensor] = None, chunk: int = 0,
+                         out: Optional[torch.Tensor] = None, validate: Optional[bool] = None,
+                         plan=None) -> torch.Tensor:
+    """grad_cbsr[num_cols, k]: the feature gradient of spgemm_forward_heads, the sum over the H
+    heads of sspmm_backward(..., values[h], grad_output[h], ..., mode="csc"), with the heads
+    summed per edge before the contribution row is stored: one selector gather, one row written
+    and one row read per edge whatever H (maxk_sspmm_backward_heads).  values [H, E],
+    grad_output [H, num_rows, D], 1 <= H <= MAX_HEADS; row_div is shared by the heads.  Two-phase
+    and atomic-free like mode "csc": bitwise repeatable, and at H == 1 bitwise that call.  Uses
+    the graph's transpose plan (cached per `indices`, or `plan=` from transpose_plan()), which
+    depends on the graph alone: weights that change every step never rebuild it.  The same
+    operand checks as the other multi-head calls."""
+    _need(values, "values", torch.float32)
+    _need(grad_output, "grad_output", torch.float32)
+    _need(indptr, "indptr", torch.int32)
+    _need(indices, "indices", torch.int32)
+    _need(cbsr_idx, "sparse_selector", torch.uint8)
+    if grad_output.dim() != 3 or not 1 <= grad_output.shape[0] <= MAX_HEADS:
+        raise RuntimeError(f"grad_output must be [H, num_rows, dim_origin] with 1 <= H <= "
+                           f"{MAX_HEADS}")
+    H, _, D = grad_output.shape
+    if cbsr_idx.dim() != 2:
+        raise RuntimeError("sparse_selector must be [V, k]")
+    num_cols, k = cbsr_idx.shape
+    num_rows = indptr.numel() - 1
+    E = indices.numel()
+    if grad_output.shape[1] != num_rows:
+        raise RuntimeError("grad_output must be [H, num_rows, dim_origin]")
+    if tuple(values.shape) != (H, E):
+        raise RuntimeError("values must be [H, num_e], H that of grad_output")
+    if row_div is not None:
+        _need(row_div, "row_div", torch.float32)
+        if row_div.numel() != num_rows:
+            raise RuntimeError("row_div must have num_rows entries")
+    _validate_call(validate, indptr, indices, num_cols, cbsr_idx, D)
+    dev = grad_output.device
+    out = _heads_out(out, (num_cols, k), dev, "[num_cols, k]")
+    col_ptr, csc_eid = plan if plan is not None else transpose_plan(indices, num_cols)
+    shape = (num_rows, num_cols, E, D, k, H, chunk)
+    _launch_ws(dev, "maxk_sspmm_backward_heads", "maxk_sspmm_backward_heads_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(grad_output), _ptr(row_div),
+                _ptr(cbsr_idx), _ptr(col_ptr), _ptr(csc_eid), _ptr(out), *shape))
+    return out
+
+
+HEADS_MAX_COLS = 1 << 24  # the multi-head entries reject tables of this many columns
+
+
+def heads_backward_route(k: int, num_e: int, num_cols: int, num_rows: int,
+                         num_heads: Optional[int] = None) -> str:
+    """How a multi-head aggregation's feature backward runs (MaxKSpGEMMHeadsFunction.backward):
+    "heads", one sspmm_backward_heads call, or "calls", H sspmm_backward calls in
+    graph_only_mode's mode added in head order.  Measured (profiles/r13/heads_bwd/, DESIGN.md
+    5.8), heads / calls at H = 2, 4, 8: Reddit-sized k = 16 0.54, 0.29, 0.16; products-sized
+    k = 32 0.53, 0.31, 0.21; products-sized k = 8, where the calls run bsort, 0.70, 0.42, 0.33
+    -- each far past the calls' run-to-run spread of at most 2.9 %, so the rule needs no
+    threshold: "heads" on every graph the entry takes.  Only one head shares nothing: the
+    single call is the same work (csc: 1.07 and 1.02) or the faster bsort (1.25), so
+    num_heads == 1, when given, returns "calls".
+    "calls" also for a table the multi-head entry rejects (HEADS_MAX_COLS columns or more) and,
+    unless MAXK_HEADS_BWD=heads|calls forces a route, when MAXK_BWD_MODE forces a backward mode
+    (graph_only_mode returns None: the forced mode is what the H calls then run)."""
+    if num_cols >= HEADS_MAX_COLS:
+        return "calls"
+    forced = os.environ.get("MAXK_HEADS_BWD", "")
+    if forced in ("heads", "calls"):
+        return forced
+    if graph_only_mode(k, num_e, num_cols) is None or num_heads == 1:
+        return "calls"
+    return "heads"
 
 
 EDGE_SEL_KMAX = 16

@@ -74,6 +74,9 @@ SIGNATURES = {
                                                _i64, _i32, _i32, _i32, _p, _sz, _p]),
     "maxk_sspmm_backward_csc_sel": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64,
                                                _i64, _i32, _i32, _i32, _p, _sz, _p]),
+    "maxk_sspmm_backward_heads_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "maxk_sspmm_backward_heads": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64,
+                                                 _i64, _i32, _i32, _i32, _i32, _p, _sz, _p]),
     "maxk_edge_selectors": (ctypes.c_int, [_p, _p, _i64, _i32, _p, _p]),
     "maxk_edge_selectors_blocks": (_i64, [_i64]),
     "maxk_transpose_plan_workspace_size": (_sz, [_i64, _i64]),

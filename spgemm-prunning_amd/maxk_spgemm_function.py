@@ -315,10 +315,12 @@ class MaxKSpGEMMHeadsFunction(Function):
     for all heads: maxk_cuda_kernels.spgemm_forward_heads / edge_weight_grad_heads); on a dense
     graph, where the multi-head forward measured no faster, the forward is H single-head calls
     into the slices of the output instead (maxk_cuda_kernels.heads_forward_route).  The
-    feature gradient is the sum over the heads, in head order, of the existing sspmm_backward
-    on (graph_values[h], grad_output[h]) in the graph-only mode the single-head function takes
-    with differentiable weights -- H launches of an existing kernel; a fused multi-head
-    feature backward is the follow-up."""
+    feature gradient, the sum over the heads, is one sspmm_backward_heads call (the heads summed
+    per edge before the contribution row is stored) where
+    maxk_cuda_kernels.heads_backward_route says "heads": two or more heads, no forced backward
+    mode; on route "calls" it is the sum, in head order, of sspmm_backward on (graph_values[h],
+    grad_output[h]) in the graph-only mode the single-head function takes with differentiable
+    weights."""
 
     @staticmethod
     def forward(ctx, graph_indptr, graph_indices, graph_values, topk_values, topk_indices,
@@ -362,7 +364,12 @@ class MaxKSpGEMMHeadsFunction(Function):
         if ctx.needs_input_grad[2]:
             grad_w = maxk_cuda_kernels.edge_weight_grad_heads(indptr, indices, vals, sel, g,
                                                               row_div=row_div).to(ctx.w_dtype)
-        if ctx.needs_input_grad[3]:
+        if ctx.needs_input_grad[3] and maxk_cuda_kernels.heads_backward_route(
+                sel.shape[1], indices.numel(), sel.shape[0], indptr.numel() - 1,
+                w.shape[0]) == "heads":
+            grad_tv = maxk_cuda_kernels.sspmm_backward_heads(indptr, indices, w, g, sel,
+                                                             row_div=row_div)
+        elif ctx.needs_input_grad[3]:
             for h in range(w.shape[0]):  # accumulated in head order
                 part = maxk_cuda_kernels.sspmm_backward(indptr, indices, w[h], g[h], sel,
                                                         row_div=row_div, mode=ctx.bwd_mode)

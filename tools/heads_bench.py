@@ -1,20 +1,28 @@
 #!/usr/bin/env python3
 """Multi-head aggregation against H calls of the single-head entries it replaces.
 
-Per workload (Reddit-sized D = 256 k = 16, products-sized D = 256 k = 32; bench.py's synthetic
-graphs and features) and per head count H, in one process, after warm-up, with device events,
-alternating within every iteration so all four see the same clocks and cache state:
+Per workload (Reddit-sized D = 256 k = 16, products-sized D = 256 k = 32 and, for the feature
+gradient, k = 8, where the single-head baseline is bsort; bench.py's synthetic graphs and
+features) and per head count H, in one process, after warm-up, with device events, alternating
+within every iteration so all of them see the same clocks and cache state:
 
   forward_heads      mk.spgemm_forward_heads         one call, values [H, E]
   forward_calls      H x mk.spgemm_forward           on the contiguous slices values[h]
   edge_grad_heads    mk.edge_weight_grad_heads       one call, grad_out [H, V, D]
   edge_grad_calls    H x mk.edge_weight_grad         on the slices grad_out[h]
+  feat_grad_heads    mk.sspmm_backward_heads         one call, values [H, E], grad_out [H, V, D]
+  feat_grad_calls    H x mk.sspmm_backward           on the slices, in graph_only_mode's mode (csc
+                                                     or bsort), and the H - 1 add_ of the results:
+                                                     MaxKSpGEMMHeadsFunction.backward's route "calls"
 
 It reports the medians, the ratio heads / calls of each pair, and the run-to-run spread of the
 single-head baselines in this run, (max - min) / median over the iterations: the heads kernel
-counts as faster only where 1 - ratio exceeds that spread.  Writes one JSON file and prints it.
+counts as faster only where 1 - ratio exceeds that spread.  For the feature gradient it also
+records the largest difference between the two results over the largest magnitude, at the size
+timed.  Writes one JSON file and prints it.
 
   python tools/heads_bench.py [--graphs reddit:16,products:32] [--heads 4,8] [--iters 20]
+                              [--pairs forward,edge_grad,feat_grad]
 """
 import argparse
 import json
@@ -47,10 +55,17 @@ def summary(ts):
                 spread=round((max(ts) - min(ts)) / med, 4), n=len(ts))
 
 
-def run(name, k, D, H, iters, warmup, seed, dev):
+PAIRS = ("forward", "edge_grad", "feat_grad")
+_GRAPH = {}  # the last graph generated: the head counts of one workload share it
+
+
+def run(name, k, D, H, iters, warmup, seed, dev, pairs=PAIRS):
     mg = bench.maxk_graph
     V = mg.PRESETS[name]["V"]
-    row_ptr, col = mg.synthetic_graph(name, seed, dev)
+    if (name, seed) not in _GRAPH:
+        _GRAPH.clear()
+        _GRAPH[(name, seed)] = mg.synthetic_graph(name, seed, dev)
+    row_ptr, col = _GRAPH[(name, seed)]
     E = col.numel()
     gen = torch.Generator(device=dev).manual_seed(123)
     w = torch.rand(H, E, generator=gen, device=dev)
@@ -58,9 +73,10 @@ def run(name, k, D, H, iters, warmup, seed, dev):
     deg = torch.diff(row_ptr).clamp(min=1).float()
     cv, ci = mk.topk_cbsr(X, k)
     del X
-    y = torch.empty(H, V, D, device=dev)
+    y = torch.empty(H if "forward" in pairs else 1, V, D, device=dev)
     G = torch.rand(H, V, D, generator=gen, device=dev)
-    ge = torch.empty(H, E, device=dev)
+    ge = torch.empty(H if "edge_grad" in pairs else 0, E, device=dev)
+    mode = mk.graph_only_mode(k, E, V)
 
     def fwd_heads():
         mk.spgemm_forward_heads(row_ptr, col, w, cv, ci, D, row_div=deg, out=y, validate=False)
@@ -78,8 +94,21 @@ def run(name, k, D, H, iters, warmup, seed, dev):
             mk.edge_weight_grad(row_ptr, col, cv, ci, G[h], row_div=deg, out=ge[h],
                                 validate=False)
 
+    def fg_heads():
+        return mk.sspmm_backward_heads(row_ptr, col, w, G, ci, row_div=deg, validate=False)
+
+    def fg_calls():
+        acc = None
+        for h in range(H):
+            part = mk.sspmm_backward(row_ptr, col, w[h], G[h], ci, row_div=deg, mode=mode,
+                                     validate=False)
+            acc = part if acc is None else acc.add_(part)
+        return acc
+
     ops = (("forward_heads", fwd_heads), ("forward_calls", fwd_calls),
-           ("edge_grad_heads", eg_heads), ("edge_grad_calls", eg_calls))
+           ("edge_grad_heads", eg_heads), ("edge_grad_calls", eg_calls),
+           ("feat_grad_heads", fg_heads), ("feat_grad_calls", fg_calls))
+    ops = tuple(o for o in ops if o[0].rsplit("_", 1)[0] in pairs)
     mk.spgemm_forward(row_ptr, col, w[0], cv, ci, D, row_div=deg, out=y[0], validate=True)
     for _ in range(warmup):
         for _, fn in ops:
@@ -90,8 +119,11 @@ def run(name, k, D, H, iters, warmup, seed, dev):
         for n, fn in ops:
             ts[n].append(timed(fn))
     s = {n: summary(t) for n, t in ts.items()}
-    r = dict(graph=name, V=V, E=E, D=D, k=k, H=H, **s)
-    for a in ("forward", "edge_grad"):
+    r = dict(graph=name, V=V, E=E, D=D, k=k, H=H, feat_grad_calls_mode=mode, **s)
+    if "feat_grad" in pairs:  # faster and different is not faster: the two results, at this size
+        a, b = fg_heads(), fg_calls()
+        r["feat_grad_max_diff_over_max"] = float((a - b).abs().max() / b.abs().max())
+    for a in pairs:
         r[f"ratio_{a}_heads_to_calls"] = round(
             s[f"{a}_heads"]["median_ms"] / s[f"{a}_calls"]["median_ms"], 4)
         r[f"{a}_heads_faster"] = bool(
@@ -107,6 +139,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--pairs", default=",".join(PAIRS))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12", "heads", "bench.json"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -115,7 +148,8 @@ def main():
     for spec in args.graphs.split(","):
         name, k = spec.split(":")
         for H in (int(h) for h in args.heads.split(",")):
-            r = run(name, int(k), args.dim, H, args.iters, args.warmup, args.seed, dev)
+            r = run(name, int(k), args.dim, H, args.iters, args.warmup, args.seed, dev,
+                    tuple(p for p in PAIRS if p in args.pairs.split(",")))
             print(json.dumps(r), flush=True)
             res["workloads"].append(r)
             torch.cuda.empty_cache()
