@@ -328,6 +328,61 @@ int maxk_gat_edge_softmax_backward(const int32_t *row_ptr, const int32_t *col_id
                                    size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Multi-head GAT edge softmax: maxk_gat_edge_softmax and its backward for H = num_heads heads
+ * over one walk of the graph -- the attention coefficients edge_val [num_heads, num_e] that
+ * maxk_spgemm_forward_heads takes, and the gradient of the scores from the grad_edge that
+ * maxk_edge_weight_grad_heads returns.  The reference has no counterpart.
+ * Layout, head-major, so every head's slice is an array the single-head entries take:
+ *   s_dst, grad_s_dst  f32 [num_heads, num_rows];   s_src, grad_s_src  f32 [num_heads, num_cols];
+ *   w, grad_w          f32 [num_heads, num_e], CSR order inside a head.
+ * 1 <= num_heads <= MAXK_MAX_HEADS, any value in the range.
+ * What the heads share: col_idx[e] is read once per edge; s_src is first copied to
+ *   ss_t [num_cols, HP] in the workspace, HP = num_heads rounded up to 2, 4 or 8 (pad heads 0,
+ *   never stored to an output), so the random read of a column's scores is one aligned
+ *   4 * HP-byte vector inside one 64-B sector for all heads; the backward writes gz edge-major,
+ *   gzT [num_e, HP], and the column sums read csc_eid once and gather one vector per CSC slot.
+ *   num_heads == 1 has nothing to share and is the single-head entry, workspace size included.
+ * Partition, item rule (chunk_edges, 0 = the same auto rule), lane assignment, sum orders and
+ *   slot merges are the single-head entries'.  For equal chunk_edges head h of w equals
+ *   maxk_gat_edge_softmax on head h's slices bitwise; the gradients equal
+ *   maxk_gat_edge_softmax_backward's within the bounds above (the same sums in the same order,
+ *   but the compiler contracts a multiply and the add it feeds differently in the two kernels),
+ *   bitwise at num_heads == 1.  Numerics, repeatability and the non-finite rules are those
+ *   stated above, per head, and head h's outputs hold head h's inputs only: they do not depend,
+ *   bitwise, on the other heads' scores or grad_w, and a NaN in s_src[h, c] reaches head h's
+ *   rows that read c and nothing else.
+ * Memory: as the single-head entries (exactly the queried size, 256-B aligned, any content, a
+ *   shorter one rejected on the host before any launch; every output element written, exact 0
+ *   for a row without edges and a column no edge reads; num_e == 0 launches nothing forward and
+ *   writes zeros backward; inputs never written; no atomics, no allocation).  The workspace
+ *   holds ss_t and num_heads times the row slots, and for the backward gzT and num_heads times
+ *   the column slots.  gzT is 4 * HP * num_e bytes, num_heads times the single-head gz that H
+ *   calls would reuse (3.7 GB against 458 MB at 8 heads and 114.6 M edges): the price of one
+ *   sector per CSC slot.
+ * Argument errors (num_heads outside [1, MAXK_MAX_HEADS], a null pointer, negative sizes,
+ *   negative_slope outside [0, 1] or NaN): MAXK_ERR_INVALID with a message, before any launch.
+ * ------------------------------------------------------------------------- */
+size_t maxk_gat_edge_softmax_heads_workspace_size(int32_t num_heads, int64_t num_rows,
+                                                  int64_t num_cols, int64_t num_e,
+                                                  int32_t chunk_edges);
+int maxk_gat_edge_softmax_heads(const int32_t *row_ptr, const int32_t *col_idx,
+                                const float *s_dst, const float *s_src, float negative_slope,
+                                float *w, int32_t num_heads, int64_t num_rows, int64_t num_cols,
+                                int64_t num_e, int32_t chunk_edges, void *workspace,
+                                size_t workspace_bytes, void *stream);
+size_t maxk_gat_edge_softmax_heads_backward_workspace_size(int32_t num_heads, int64_t num_rows,
+                                                           int64_t num_cols, int64_t num_e,
+                                                           int32_t chunk_edges);
+int maxk_gat_edge_softmax_heads_backward(const int32_t *row_ptr, const int32_t *col_idx,
+                                         const int32_t *col_ptr, const int32_t *csc_eid,
+                                         const float *s_dst, const float *s_src,
+                                         float negative_slope, const float *w,
+                                         const float *grad_w, float *grad_s_dst,
+                                         float *grad_s_src, int32_t num_heads, int64_t num_rows,
+                                         int64_t num_cols, int64_t num_e, int32_t chunk_edges,
+                                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Backward outer-product sampled SpMM (SSpMM):
  *   grad_cbsr[c,l] = sum_{e=(r->c)} edge_val[e] * grad_out[r, cbsr_idx[c,l]] / row_div[r]
  *                  = (A^T diag(1/row_div) G)[c, cbsr_idx[c,l]]     (from the CSR of A)

@@ -49,6 +49,7 @@ __all__ = [
     "edge_softmax", "edge_softmax_backward", "gat_edge_softmax", "gat_edge_softmax_backward",
     "spgemm_forward_heads", "edge_weight_grad_heads", "MAX_HEADS", "heads_forward_route",
     "sspmm_backward_heads", "heads_backward_route",
+    "gat_edge_softmax_heads", "gat_edge_softmax_heads_backward", "heads_softmax_route",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -575,6 +576,90 @@ def gat_edge_softmax_backward(indptr: torch.Tensor, indices: torch.Tensor, s_dst
                 _ptr(s_src), float(negative_slope), _ptr(w), _ptr(grad_w), _ptr(g_dst),
                 _ptr(g_src), *shape))
     return g_dst, g_src
+
+
+def _gat_heads_operands(indptr, indices, s_dst, s_src):
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (s_dst, "s_dst", torch.float32), (s_src, "s_src", torch.float32)):
+        _need(t, n, dt)
+    num_rows = indptr.numel() - 1
+    if s_dst.dim() != 2 or not 1 <= s_dst.shape[0] <= MAX_HEADS or s_dst.shape[1] != num_rows:
+        raise RuntimeError(f"s_dst must be [H, num_rows] with 1 <= H <= {MAX_HEADS}")
+    if s_src.dim() != 2 or s_src.shape[0] != s_dst.shape[0]:
+        raise RuntimeError("s_src must be [H, num_cols]")
+    return s_dst.shape[0], num_rows, s_src.shape[1], indices.numel()
+
+
+def gat_edge_softmax_heads(indptr: torch.Tensor, indices: torch.Tensor, s_dst: torch.Tensor,
+                           s_src: torch.Tensor, negative_slope: float = 0.2, chunk: int = 0,
+                           out: Optional[torch.Tensor] = None,
+                           validate: Optional[bool] = None) -> torch.Tensor:
+    """w[H, E] float32: gat_edge_softmax for H heads, s_dst [H, num_rows] and s_src
+    [H, num_cols], over one walk of the graph: indices and a column's H scores are read once per
+    edge (maxk_gat_edge_softmax_heads).  1 <= H <= MAX_HEADS.  Head h's slice is bitwise
+    gat_edge_softmax(..., s_dst[h], s_src[h], ...) at the same chunk."""
+    H, num_rows, num_cols, E = _gat_heads_operands(indptr, indices, s_dst, s_src)
+    _validate_rows(validate, indptr, indices, num_cols, E)
+    dev = s_src.device
+    out = _heads_out(out, (H, E), dev, "[H, num_e]")
+    shape = (num_rows, num_cols, E, chunk)
+    _launch_ws(dev, "maxk_gat_edge_softmax_heads", "maxk_gat_edge_softmax_heads_workspace_size",
+               (H,) + shape, (_ptr(indptr), _ptr(indices), _ptr(s_dst), _ptr(s_src),
+                              float(negative_slope), _ptr(out), H, *shape))
+    return out
+
+
+def gat_edge_softmax_heads_backward(indptr: torch.Tensor, indices: torch.Tensor,
+                                    s_dst: torch.Tensor, s_src: torch.Tensor, w: torch.Tensor,
+                                    grad_w: torch.Tensor, negative_slope: float = 0.2,
+                                    chunk: int = 0,
+                                    out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                                    validate: Optional[bool] = None):
+    """(grad_s_dst [H, num_rows], grad_s_src [H, num_cols]) of gat_edge_softmax_heads from its
+    w [H, E] and the gradient of w (maxk_gat_edge_softmax_heads_backward): one read of indices,
+    of a column's H scores and of a CSC slot's H values per edge.  The workspace holds an
+    [E, HP] float buffer (HP = H rounded up to 2, 4 or 8), H times the single-head call's.
+    Head h's slices equal gat_edge_softmax_backward on head h's slices within its bound, and
+    bitwise at H = 1 (one head is the single-head call)."""
+    H, num_rows, num_cols, E = _gat_heads_operands(indptr, indices, s_dst, s_src)
+    _need(w, "w", torch.float32)
+    _need(grad_w, "grad_w", torch.float32)
+    if tuple(w.shape) != (H, E) or tuple(grad_w.shape) != (H, E):
+        raise RuntimeError("w and grad_w must be [H, num_e]")
+    _validate_rows(validate, indptr, indices, num_cols, E)
+    dev = s_src.device
+    col_ptr, csc_eid = transpose_plan(indices, num_cols)
+    if out is None:
+        g_dst = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
+        g_src = torch.empty(H, num_cols, dtype=torch.float32, device=dev)
+    else:
+        g_dst, g_src = out
+        _need(g_dst, "out[0]", torch.float32)
+        _need(g_src, "out[1]", torch.float32)
+        if tuple(g_dst.shape) != (H, num_rows) or tuple(g_src.shape) != (H, num_cols):
+            raise RuntimeError("out must be ([H, num_rows], [H, num_cols])")
+    shape = (num_rows, num_cols, E, chunk)
+    _launch_ws(dev, "maxk_gat_edge_softmax_heads_backward",
+               "maxk_gat_edge_softmax_heads_backward_workspace_size", (H,) + shape,
+               (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(s_dst),
+                _ptr(s_src), float(negative_slope), _ptr(w), _ptr(grad_w), _ptr(g_dst),
+                _ptr(g_src), H, *shape))
+    return g_dst, g_src
+
+
+def heads_softmax_route(num_heads: int, num_rows: int, num_e: int) -> str:
+    """How the attention coefficients of a multi-head GAT layer are computed
+    (maxk_layers.gat_edge_softmax_heads): "heads", one gat_edge_softmax_heads call and one
+    backward, or "calls", the single-head pass per head.  "heads" from two heads on, on every
+    graph: measured against the H calls in the same run, Reddit-sized and products-sized, at
+    H = 2, 4 and 8, each direction gains 26 to 68 % against spreads of at most 3.4 %
+    (profiles/r14/heads_softmax/), so the rule has no threshold and num_rows and
+    num_e do not enter it.  One head takes "calls": there is nothing to share.
+    MAXK_HEADS_SOFTMAX=heads|calls forces one."""
+    forced = os.environ.get("MAXK_HEADS_SOFTMAX", "")
+    if forced in ("heads", "calls"):
+        return forced
+    return "heads" if num_heads >= 2 else "calls"
 
 
 def records_ok(num_rows: int, num_cols: int, num_e: int, dim_origin: int, k: int) -> bool:

@@ -376,6 +376,28 @@ class GATEdgeSoftmax(Function):
         return None, None, g_dst.to(ctx.dtypes[0]), g_src.to(ctx.dtypes[1]), None
 
 
+class GATEdgeSoftmaxHeads(Function):
+    """alpha [H, E] of H GAT heads from s_dst [H, V] and s_src [H, V] in one pass each way
+    (maxk_gat_edge_softmax_heads / _backward): the column index and a column's H scores are read
+    once per edge.  Saves alpha and the scores, as GATEdgeSoftmax does."""
+
+    @staticmethod
+    def forward(ctx, indptr, indices, s_dst, s_src, negative_slope):
+        sd, ss = s_dst.float().contiguous(), s_src.float().contiguous()
+        w = mk.gat_edge_softmax_heads(indptr, indices, sd, ss, negative_slope)
+        ctx.save_for_backward(indptr, indices, sd, ss, w)
+        ctx.slope = float(negative_slope)
+        ctx.dtypes = (s_dst.dtype, s_src.dtype)
+        return w
+
+    @staticmethod
+    def backward(ctx, grad_w):
+        indptr, indices, sd, ss, w = ctx.saved_tensors
+        g_dst, g_src = mk.gat_edge_softmax_heads_backward(indptr, indices, sd, ss, w,
+                                                          grad_w.float().contiguous(), ctx.slope)
+        return None, None, g_dst.to(ctx.dtypes[0]), g_src.to(ctx.dtypes[1]), None
+
+
 def edge_softmax(graph: CSRGraph, logits: torch.Tensor) -> torch.Tensor:
     """Softmax of logits [E] (CSR order) over each destination's incoming edges."""
     return EdgeSoftmax.apply(graph.indptr, logits)
@@ -390,9 +412,15 @@ def gat_edge_softmax(graph: CSRGraph, s_dst: torch.Tensor, s_src: torch.Tensor,
 
 def gat_edge_softmax_heads(graph: CSRGraph, s_dst: torch.Tensor, s_src: torch.Tensor,
                            negative_slope: float = 0.2) -> torch.Tensor:
-    """alpha [H, E] float32 of H GAT heads from their scores s_dst [H, V], s_src [H, V]: the
-    single-head pass on each head's contiguous slice, stacked."""
+    """alpha [H, E] float32 of H GAT heads from their scores s_dst [H, V], s_src [H, V]: one
+    multi-head pass (GATEdgeSoftmaxHeads) or the single-head pass on each head's contiguous
+    slice, stacked, as mk.heads_softmax_route says.  The two give the same alpha, byte for byte,
+    and gradients within the kernels' bounds of each other."""
     s_dst, s_src = s_dst.contiguous(), s_src.contiguous()
+    if mk.heads_softmax_route(s_dst.shape[0], graph.indptr.numel() - 1,
+                              graph.indices.numel()) == "heads":
+        return GATEdgeSoftmaxHeads.apply(graph.indptr, graph.indices, s_dst, s_src,
+                                         negative_slope)
     return torch.stack([GATEdgeSoftmax.apply(graph.indptr, graph.indices, s_dst[h], s_src[h],
                                              negative_slope) for h in range(s_dst.shape[0])])
 

@@ -15,6 +15,13 @@ within every iteration so all of them see the same clocks and cache state:
                                                      or bsort), and the H - 1 add_ of the results:
                                                      MaxKSpGEMMHeadsFunction.backward's route "calls"
 
+  softmax_fwd_heads  mk.gat_edge_softmax_heads       one call, s_dst / s_src [H, V]   (--pairs softmax)
+  softmax_fwd_calls  H x mk.gat_edge_softmax         on the slices
+  softmax_bwd_heads  mk.gat_edge_softmax_heads_backward   one call, w / grad_w [H, E]
+  softmax_bwd_calls  H x mk.gat_edge_softmax_backward     on the slices
+  layer_heads / layer_calls   MaxKMultiHeadGATConv forward plus backward under
+                     MAXK_HEADS_SOFTMAX=heads / =calls, out_feats = D / H       (--pairs layer)
+
 It reports the medians, the ratio heads / calls of each pair, and the run-to-run spread of the
 single-head baselines in this run, (max - min) / median over the iterations: the heads kernel
 counts as faster only where 1 - ratio exceeds that spread.  For the feature gradient it also
@@ -23,6 +30,7 @@ timed.  Writes one JSON file and prints it.
 
   python tools/heads_bench.py [--graphs reddit:16,products:32] [--heads 4,8] [--iters 20]
                               [--pairs forward,edge_grad,feat_grad]
+  python tools/heads_bench.py --pairs softmax,layer --heads 1,2,4,8 --out FILE
 """
 import argparse
 import json
@@ -131,6 +139,121 @@ def run(name, k, D, H, iters, warmup, seed, dev, pairs=PAIRS):
     return r
 
 
+SOFTMAX_PAIRS = ("softmax_fwd", "softmax_bwd")
+
+
+def _graph(name, seed, dev):
+    if (name, seed) not in _GRAPH:
+        _GRAPH.clear()
+        _GRAPH[(name, seed)] = bench.maxk_graph.synthetic_graph(name, seed, dev)
+    return _GRAPH[(name, seed)]
+
+
+def _pair_ratios(r, s, pairs):
+    for a in pairs:
+        r[f"ratio_{a}_heads_to_calls"] = round(
+            s[f"{a}_heads"]["median_ms"] / s[f"{a}_calls"]["median_ms"], 4)
+        r[f"{a}_heads_faster"] = bool(
+            1.0 - r[f"ratio_{a}_heads_to_calls"] > s[f"{a}_calls"]["spread"])
+
+
+def run_softmax(name, H, iters, warmup, seed, dev, slope=0.2):
+    """mk.gat_edge_softmax_heads and its backward against exactly the H single-head calls each
+    replaces, alternating; the largest difference between the two results at this size."""
+    V = bench.maxk_graph.PRESETS[name]["V"]
+    row_ptr, col = _graph(name, seed, dev)
+    E = col.numel()
+    gen = torch.Generator(device=dev).manual_seed(321)
+    sd = torch.randn(H, V, generator=gen, device=dev)
+    ss = torch.randn(H, V, generator=gen, device=dev)
+    gw = torch.randn(H, E, generator=gen, device=dev)
+    w_h, w_c = torch.empty(H, E, device=dev), torch.empty(H, E, device=dev)
+    g_h = (torch.empty(H, V, device=dev), torch.empty(H, V, device=dev))
+    g_c = (torch.empty(H, V, device=dev), torch.empty(H, V, device=dev))
+    mk.transpose_plan(col, V)  # once per graph, as in training: not part of either side
+
+    def fwd_heads():
+        mk.gat_edge_softmax_heads(row_ptr, col, sd, ss, slope, out=w_h, validate=False)
+
+    def fwd_calls():
+        for h in range(H):
+            mk.gat_edge_softmax(row_ptr, col, sd[h], ss[h], slope, out=w_c[h], validate=False)
+
+    def bwd_heads():
+        mk.gat_edge_softmax_heads_backward(row_ptr, col, sd, ss, w_h, gw, slope, out=g_h,
+                                           validate=False)
+
+    def bwd_calls():
+        for h in range(H):
+            mk.gat_edge_softmax_backward(row_ptr, col, sd[h], ss[h], w_c[h], gw[h], slope,
+                                         out=(g_c[0][h], g_c[1][h]), validate=False)
+
+    ops = (("softmax_fwd_heads", fwd_heads), ("softmax_fwd_calls", fwd_calls),
+           ("softmax_bwd_heads", bwd_heads), ("softmax_bwd_calls", bwd_calls))
+    mk.gat_edge_softmax(row_ptr, col, sd[0], ss[0], slope, out=w_c[0], validate=True)
+    for _ in range(warmup):
+        for _, fn in ops:
+            fn()
+    torch.cuda.synchronize()
+    ts = {n: [] for n, _ in ops}
+    for _ in range(iters):
+        for n, fn in ops:
+            ts[n].append(timed(fn))
+    s = {n: summary(t) for n, t in ts.items()}
+    r = dict(kind="softmax", graph=name, V=V, E=E, H=H, **s)
+    r["w_bitwise_equal"] = bool(torch.equal(w_h.view(torch.int32), w_c.view(torch.int32)))
+    r["w_max_abs_diff"] = float((w_h - w_c).abs().max())
+    for what, a, b in (("grad_s_dst", g_h[0], g_c[0]), ("grad_s_src", g_h[1], g_c[1])):
+        r[f"{what}_max_diff_over_max"] = float((a - b).abs().max() / b.abs().max())
+    r["workspace_bytes_heads_bwd"] = int(mk._lib().maxk_gat_edge_softmax_heads_backward_workspace_size(
+        H, V, V, E, 0))
+    r["workspace_bytes_single_bwd"] = int(mk._lib().maxk_gat_edge_softmax_backward_workspace_size(
+        V, V, E, 0))
+    _pair_ratios(r, s, SOFTMAX_PAIRS)
+    return r
+
+
+def run_layer(name, k, D, H, iters, warmup, seed, dev):
+    """MaxKMultiHeadGATConv forward plus backward under MAXK_HEADS_SOFTMAX=calls against =heads,
+    alternating; out_feats = D / H."""
+    import maxk_layers as ML
+    V = bench.maxk_graph.PRESETS[name]["V"]
+    row_ptr, col = _graph(name, seed, dev)
+    graph = ML.CSRGraph(row_ptr, col)
+    torch.manual_seed(7)
+    conv = ML.MaxKMultiHeadGATConv(D, D // H, H).to(dev)
+    xs, vals, idx = ML.maxk(torch.rand(V, D, device=dev), k)
+    xs = xs.detach().requires_grad_(True)
+    vals = vals.detach().requires_grad_(True)
+
+    def step(route):
+        os.environ["MAXK_HEADS_SOFTMAX"] = route
+        conv.zero_grad(set_to_none=True)
+        xs.grad = vals.grad = None
+        conv(graph, xs, vals, idx).sum().backward()
+
+    routes = ("heads", "calls")
+    saved = os.environ.get("MAXK_HEADS_SOFTMAX")
+    try:
+        for _ in range(warmup):
+            for route in routes:
+                step(route)
+        torch.cuda.synchronize()
+        ts = {route: [] for route in routes}
+        for _ in range(iters):
+            for route in routes:
+                ts[route].append(timed(lambda: step(route)))
+    finally:
+        if saved is None:
+            os.environ.pop("MAXK_HEADS_SOFTMAX", None)
+        else:
+            os.environ["MAXK_HEADS_SOFTMAX"] = saved
+    s = {f"layer_{route}": summary(t) for route, t in ts.items()}
+    r = dict(kind="layer", graph=name, V=V, E=col.numel(), D=D, k=k, H=H, out_feats=D // H, **s)
+    _pair_ratios(r, s, ("layer",))
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--graphs", default="reddit:16,products:32")
@@ -145,13 +268,23 @@ def main():
     dev = torch.device("cuda:0")
     res = dict(device=torch.cuda.get_device_name(0), iters=args.iters, warmup=args.warmup,
                build_config=mk._lib().maxk_build_config().decode(), workloads=[])
+    asked = args.pairs.split(",")
+    pairs = tuple(p for p in PAIRS if p in asked)
     for spec in args.graphs.split(","):
         name, k = spec.split(":")
         for H in (int(h) for h in args.heads.split(",")):
-            r = run(name, int(k), args.dim, H, args.iters, args.warmup, args.seed, dev,
-                    tuple(p for p in PAIRS if p in args.pairs.split(",")))
-            print(json.dumps(r), flush=True)
-            res["workloads"].append(r)
+            rs = []
+            if pairs:
+                rs.append(run(name, int(k), args.dim, H, args.iters, args.warmup, args.seed, dev,
+                              pairs))
+            if "softmax" in asked:
+                rs.append(run_softmax(name, H, args.iters, args.warmup, args.seed, dev))
+            if "layer" in asked and H >= 2:
+                rs.append(run_layer(name, int(k), args.dim, H, args.iters, args.warmup,
+                                    args.seed, dev))
+            for r in rs:
+                print(json.dumps(r), flush=True)
+                res["workloads"].append(r)
             torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
