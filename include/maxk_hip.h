@@ -383,6 +383,74 @@ int maxk_gat_edge_softmax_heads_backward(const int32_t *row_ptr, const int32_t *
                                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Fused multi-head GAT attention: the edge softmax inside the aggregation walk,
+ *   out[h, r, cbsr_idx[c,l]] += alpha[h,e] * cbsr_val[c,l]        e in row r, c = col_idx[e]
+ *   alpha[h,e] = exp(l_he - m_hr) / z_hr,   l_he = leaky_relu(s_dst[h,r] + s_src[h,c]),
+ *   m_hr = max_e l_he,   z_hr = sum_e exp(l_he - m_hr)
+ * -- maxk_gat_edge_softmax_heads followed by maxk_spgemm_forward_heads in one walk of the graph.
+ * alpha [num_heads, num_e] exists nowhere, not in an output and not in the workspace: the
+ * outputs are out [num_heads, num_rows, dim_origin] and the row statistics row_max = m and
+ * row_sum = z, f32 [num_heads, num_rows], from which maxk_gat_edge_alpha_heads rebuilds
+ *   w[h,e] = exp(l_he - row_max[h,r]) / row_sum[h,r]          f32 [num_heads, num_e], CSR order
+ * for the backward (one col_idx read and one score-vector gather per edge, no reductions).  The
+ * reference has no counterpart.  Head-major layout as above; 1 <= num_heads <= MAXK_MAX_HEADS,
+ * any value, one head included (there is no single-head entry to hand off to).  There is no
+ * row_div: attention rows are normalised by z.
+ * Per row piece the kernel sweeps the scores once for the piece's maximum per head, then
+ *   gathers one record per edge for all heads with p = exp(l - m_piece), summing p * value in
+ *   LDS and p per head: nothing is rescaled per edge.  A row inside one work item is stored as
+ *   sum / z; a hub row cut over items leaves unnormalised pieces with their (m, z), merged in
+ *   item order: m = max m_i, each piece scaled by exp(m_i - m), one division.  No global and no
+ *   LDS atomics.
+ * Shapes: any 1 <= dim_k <= dim_origin <= 256 (dim_k % 4 != 0, odd dim_origin, dim_k > 64), any
+ *   num_rows != num_cols; num_e == 0 writes zeros to all of out and both statistics; a table
+ *   past 2^24 columns or 4 GiB of packed records is rejected with MAXK_ERR_INVALID.  There is
+ *   no dense route and no _sel / records form.
+ * Writes: every element of out, row_max and row_sum (the alpha entry: every edge of w;
+ *   num_e == 0 launches nothing).  A row without edges gives exact zeros in all three; a column
+ *   of out that no edge of the row selects is exactly 0.
+ * Numerics (tests/gat_attention_ref.py; u = 2^-24): the composition of the two bounds above.
+ *   Each weight is within (n_r + 24 + 16 A_r) * u * alpha + (n_r + 16) * 2^-149 -- the edge
+ *   softmax's bound with 8 u more for a cut row's second exp and scale product -- carried
+ *   through the sum, plus (n + 8) * u * sum|alpha * value| with the subnormal floor, n the
+ *   element's number of addends.  row_max is within 2 A_r u of exact, row_sum within the
+ *   weight bound's relative part.  w from the statistics is within the edge softmax's bound.
+ * Non-finite values follow the IEEE evaluation of the formulas, as the two entries composed:
+ *   a row with a NaN or +Inf logit is NaN wherever it has an addend (and 0 elsewhere), a -Inf
+ *   logit contributes exactly 0, a row of only -Inf is NaN wherever it has an addend; a NaN in
+ *   s_src[h, c] reaches head h's rows that read c and nothing else.
+ * Bitwise repeatable for equal arguments whatever the workspace held (every sum's order is
+ *   fixed by the graph, chunk_edges, dim_k and num_heads); head h's slices of the three outputs
+ *   do not depend, bitwise, on the other heads' scores.
+ * Memory, as the top comment: the workspace (packed records, ss_t [num_cols, HP], per-head
+ *   slabs and statistics of the cut rows; for the alpha entry ss_t alone) is exactly the queried
+ *   size, 256-B aligned, and may hold anything; a shorter one is rejected ("workspace too
+ *   small") on the host before any launch; nothing is written outside the outputs and the
+ *   workspace, inputs are never written; no allocation, copy or synchronisation.
+ * Argument errors (num_heads outside [1, MAXK_MAX_HEADS], a null pointer, negative sizes,
+ *   negative_slope outside [0, 1] or NaN, k / D range): MAXK_ERR_INVALID with a message naming
+ *   the argument, before any launch.
+ * chunk_edges: tokens per wavefront work item, 0 = the forward's auto rule.
+ * ------------------------------------------------------------------------- */
+size_t maxk_gat_attention_heads_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                               int32_t dim_origin, int32_t dim_k,
+                                               int32_t num_heads, int32_t chunk_edges);
+int maxk_gat_attention_heads(const int32_t *row_ptr, const int32_t *col_idx, const float *s_dst,
+                             const float *s_src, float negative_slope, const float *cbsr_val,
+                             const uint8_t *cbsr_idx, float *out, float *row_max, float *row_sum,
+                             int64_t num_rows, int64_t num_cols, int64_t num_e,
+                             int32_t dim_origin, int32_t dim_k, int32_t num_heads,
+                             int32_t chunk_edges, void *workspace, size_t workspace_bytes,
+                             void *stream);
+size_t maxk_gat_edge_alpha_heads_workspace_size(int32_t num_heads, int64_t num_rows,
+                                                int64_t num_cols, int64_t num_e);
+int maxk_gat_edge_alpha_heads(const int32_t *row_ptr, const int32_t *col_idx, const float *s_dst,
+                              const float *s_src, float negative_slope, const float *row_max,
+                              const float *row_sum, float *w, int32_t num_heads,
+                              int64_t num_rows, int64_t num_cols, int64_t num_e, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Backward outer-product sampled SpMM (SSpMM):
  *   grad_cbsr[c,l] = sum_{e=(r->c)} edge_val[e] * grad_out[r, cbsr_idx[c,l]] / row_div[r]
  *                  = (A^T diag(1/row_div) G)[c, cbsr_idx[c,l]]     (from the CSR of A)

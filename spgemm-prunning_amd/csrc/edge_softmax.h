@@ -558,7 +558,7 @@ struct SlotLayout {
     int chunk, n_items;
     size_t row_off, a_off, b_off, end;
 };
-SlotLayout slot_layout(int64_t n, int64_t num_e, int chunk, size_t base) {
+inline SlotLayout slot_layout(int64_t n, int64_t num_e, int chunk, size_t base) {
     SlotLayout L{};
     L.chunk = esm_chunk(n + num_e, chunk);
     L.n_items = token_items(n, num_e, L.chunk);
@@ -573,7 +573,7 @@ dim3 item_grid(int n_items) {
     const int64_t blocks = ceil_div(n_items, kWavesPerBlock);
     return dim3((unsigned)(MAXK_FWD_XCD ? xcd_grid(blocks) : blocks));
 }
-dim3 slot_grid(int n_items) { return dim3((unsigned)ceil_div(2 * (int64_t)n_items, kBlock)); }
+inline dim3 slot_grid(int n_items) { return dim3((unsigned)ceil_div(2 * (int64_t)n_items, kBlock)); }
 
 int check_sizes(int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t chunk_edges) {
     MAXK_REQUIRE(num_rows >= 0 && num_rows < (1LL << 31), "num_rows out of range: %lld",

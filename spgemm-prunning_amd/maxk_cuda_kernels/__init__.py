@@ -50,6 +50,7 @@ __all__ = [
     "spgemm_forward_heads", "edge_weight_grad_heads", "MAX_HEADS", "heads_forward_route",
     "sspmm_backward_heads", "heads_backward_route",
     "gat_edge_softmax_heads", "gat_edge_softmax_heads_backward", "heads_softmax_route",
+    "gat_attention_heads", "gat_edge_alpha_heads", "heads_attention_route",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -660,6 +661,80 @@ def heads_softmax_route(num_heads: int, num_rows: int, num_e: int) -> str:
     if forced in ("heads", "calls"):
         return forced
     return "heads" if num_heads >= 2 else "calls"
+
+
+def gat_attention_heads(indptr: torch.Tensor, indices: torch.Tensor, s_dst: torch.Tensor,
+                        s_src: torch.Tensor, cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor,
+                        dim_origin: int, negative_slope: float = 0.2, chunk: int = 0,
+                        out: Optional[torch.Tensor] = None, validate: Optional[bool] = None):
+    """(out [H, num_rows, D], row_max [H, num_rows], row_sum [H, num_rows]): the attention
+    aggregation of H GAT heads in one walk of the graph (maxk_gat_attention_heads) -- what
+    gat_edge_softmax_heads followed by spgemm_forward_heads compute, without the coefficients
+    [H, E] ever being stored.  row_max and row_sum are the softmax statistics of every row and
+    head (the largest logit and the sum of exp(logit - max)); gat_edge_alpha_heads rebuilds the
+    coefficients from them.  1 <= H <= MAX_HEADS; bitwise repeatable."""
+    D = int(dim_origin)
+    H, num_rows, num_cols, E = _gat_heads_operands(indptr, indices, s_dst, s_src)
+    _, cols2, k = _heads_operands(indptr, indices, cbsr_val, cbsr_idx, None, validate, D)
+    if cols2 != num_cols:
+        raise RuntimeError("s_src must be [H, num_cols] with num_cols = input_data.shape[0]")
+    dev = cbsr_val.device
+    out = _heads_out(out, (H, num_rows, D), dev, "[H, num_rows, dim_origin]")
+    row_max = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
+    row_sum = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
+    shape = (num_rows, num_cols, E, D, k, H, chunk)
+    _launch_ws(dev, "maxk_gat_attention_heads", "maxk_gat_attention_heads_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(s_dst), _ptr(s_src), float(negative_slope),
+                _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), _ptr(row_max), _ptr(row_sum), *shape))
+    return out, row_max, row_sum
+
+
+def gat_edge_alpha_heads(indptr: torch.Tensor, indices: torch.Tensor, s_dst: torch.Tensor,
+                         s_src: torch.Tensor, row_max: torch.Tensor, row_sum: torch.Tensor,
+                         negative_slope: float = 0.2, out: Optional[torch.Tensor] = None,
+                         validate: Optional[bool] = None) -> torch.Tensor:
+    """w[H, E] float32: the attention coefficients from the scores and the row statistics of
+    gat_attention_heads, exp(logit - row_max) / row_sum per edge (maxk_gat_edge_alpha_heads):
+    one read of indices and one gather of a column's H scores per edge, no reductions.  Within
+    gat_edge_softmax_heads's bound of its w."""
+    H, num_rows, num_cols, E = _gat_heads_operands(indptr, indices, s_dst, s_src)
+    _need(row_max, "row_max", torch.float32)
+    _need(row_sum, "row_sum", torch.float32)
+    if tuple(row_max.shape) != (H, num_rows) or tuple(row_sum.shape) != (H, num_rows):
+        raise RuntimeError("row_max and row_sum must be [H, num_rows]")
+    _validate_rows(validate, indptr, indices, num_cols, E)
+    dev = s_src.device
+    out = _heads_out(out, (H, E), dev, "[H, num_e]")
+    shape = (H, num_rows, num_cols, E)
+    _launch_ws(dev, "maxk_gat_edge_alpha_heads", "maxk_gat_edge_alpha_heads_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(s_dst), _ptr(s_src), float(negative_slope),
+                _ptr(row_max), _ptr(row_sum), _ptr(out), *shape))
+    return out
+
+
+def heads_attention_route(num_heads: int, num_rows: int, num_e: int) -> Tuple[str, str]:
+    """(forward under no_grad, training step): how a multi-head GAT layer's attention should run,
+    "fused" (gat_attention_heads: no [H, E] tensor; the row statistics are saved and the
+    coefficients rebuilt in the backward) or "stored" (gat_edge_softmax_heads, then the
+    aggregation over the stored coefficients).  Measured against exactly what each replaces, in
+    the same run (profiles/r15/gat_attention/), fused / stored at H = 1, 2, 4, 8:
+    the forward on the Reddit-sized graph, k = 16 (dense: the stored forward is H single-head
+    calls) 1.07, 0.90, 0.85, 0.98 against spreads below 1 %; on the products-sized graph,
+    k = 32 (sparse: its records are random memory lines, and the fused walk keeps fewer waves
+    resident) 1.16, 1.06, 1.13, 1.31; the layer's forward plus backward 1.02 to 1.13 on both,
+    because the backward pays gat_edge_alpha_heads on top of the stored path's.  So: the
+    forward is "fused" on a dense graph (average degree of at least HEADS_SPARSE_DEGREE, the
+    regime of heads_forward_route) from two heads on, "stored" otherwise, and the training step
+    is "stored" everywhere.  "fused" remains the memory-saving option: it never holds the
+    4 * H * E bytes of the coefficients between forward and backward (3.6 GB of an 18.4 GB
+    step at 8 heads, Reddit-sized).  MAXK_HEADS_ATTN=fused|stored forces both.
+    MaxKMultiHeadGATConv's default does not follow this function: its `attention` argument
+    defaults to "stored"."""
+    forced = os.environ.get("MAXK_HEADS_ATTN", "")
+    if forced in ("fused", "stored"):
+        return forced, forced
+    dense = num_e >= HEADS_SPARSE_DEGREE * num_rows
+    return ("fused" if dense and num_heads >= 2 else "stored"), "stored"
 
 
 def records_ok(num_rows: int, num_cols: int, num_e: int, dim_origin: int, k: int) -> bool:

@@ -32,6 +32,7 @@ fallback, i.e. the normalised aggregation; compat mode computes that fallback th
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -39,7 +40,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 import maxk_cuda_kernels as mk
-from maxk_spgemm_function import maxk_spgemm, maxk_spgemm_heads
+from maxk_spgemm_function import maxk_gat_attention_heads, maxk_spgemm, maxk_spgemm_heads
 
 
 def _clamped(graph, name: str) -> torch.Tensor:
@@ -92,6 +93,14 @@ class CSRGraph:
         record gather per edge serving all heads (maxk_spgemm_heads)."""
         return maxk_spgemm_heads(self.indptr, self.indices, values, topk_values, topk_indices,
                                  dim, row_div)
+
+    def attend_heads(self, topk_values, topk_indices, dim: int, s_dst, s_src,
+                     negative_slope: float = 0.2):
+        """[H, V, dim]: the attention aggregation of H GAT heads from their scores s_dst [H, V]
+        and s_src [H, V] with the softmax inside the walk (maxk_gat_attention_heads): what
+        gat_edge_softmax_heads followed by aggregate_heads give, without alpha [H, E] stored."""
+        return maxk_gat_attention_heads(self.indptr, self.indices, s_dst, s_src, topk_values,
+                                        topk_indices, dim, negative_slope)
 
 
 class MaxK(Function):
@@ -478,11 +487,20 @@ class MaxKMultiHeadGATConv(nn.Module):
     of all heads from one multi-head call on the CBSR (CSRGraph.aggregate_heads: one record
     gather per edge whatever H), agg [H, V, in]; the Linear follows it as one bmm.  Gradients
     reach fc.weight, both attention matrices, x_sparse through the scores and topk_values
-    through the aggregation."""
+    through the aggregation.
+
+    attention="stored" (the default) keeps alpha [H, E] between forward and backward;
+    attention="fused" computes the softmax inside the aggregation walk
+    (CSRGraph.attend_heads), keeps the row statistics [H, V] instead and rebuilds alpha as a
+    transient in the backward.  MAXK_HEADS_ATTN=fused|stored overrides the argument."""
 
     def __init__(self, in_feats: int, out_feats: int, num_heads: int,
-                 negative_slope: float = 0.2, bias: bool = True, activation=None):
+                 negative_slope: float = 0.2, bias: bool = True, activation=None,
+                 attention: str = "stored"):
         super().__init__()
+        if attention not in ("stored", "fused"):
+            raise ValueError(f'attention must be "stored" or "fused", got {attention!r}')
+        self.attention = attention
         if not 1 <= int(num_heads) <= mk.MAX_HEADS:
             raise ValueError(f"num_heads must be in [1, {mk.MAX_HEADS}], got {num_heads}")
         self.in_feats, self.out_feats, self.num_heads = in_feats, out_feats, int(num_heads)
@@ -497,6 +515,12 @@ class MaxKMultiHeadGATConv(nn.Module):
         nn.init.xavier_normal_(self.attn_src, gain=gain)
         nn.init.xavier_normal_(self.attn_dst, gain=gain)
 
+    def attention_mode(self) -> str:
+        """"fused" or "stored": MAXK_HEADS_ATTN when it names one, else the `attention`
+        argument."""
+        forced = os.environ.get("MAXK_HEADS_ATTN", "")
+        return forced if forced in ("fused", "stored") else self.attention
+
     def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices):
         H, O = self.num_heads, self.out_feats
         W = self.fc.weight.view(H, O, self.in_feats)
@@ -504,8 +528,12 @@ class MaxKMultiHeadGATConv(nn.Module):
         v = torch.cat((torch.einsum("hoi,ho->ih", W, self.attn_dst),
                        torch.einsum("hoi,ho->ih", W, self.attn_src)), 1)  # [in, 2H]
         s = (x_sparse @ v).t().contiguous()                               # [2H, V]
-        alpha = gat_edge_softmax_heads(graph, s[:H], s[H:], self.negative_slope)
-        agg = graph.aggregate_heads(topk_values, topk_indices, self.in_feats, alpha)
+        if self.attention_mode() == "fused":
+            agg = graph.attend_heads(topk_values, topk_indices, self.in_feats, s[:H], s[H:],
+                                     self.negative_slope)
+        else:
+            alpha = gat_edge_softmax_heads(graph, s[:H], s[H:], self.negative_slope)
+            agg = graph.aggregate_heads(topk_values, topk_indices, self.in_feats, alpha)
         rst = torch.bmm(agg, W.transpose(1, 2)).transpose(0, 1)          # [V, H, out]
         if self.bias is not None:
             rst = rst + self.bias

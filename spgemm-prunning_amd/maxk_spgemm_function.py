@@ -387,6 +387,78 @@ def maxk_spgemm_heads(graph_indptr, graph_indices, graph_values, topk_values, to
                                          topk_indices, dim_origin, degrees)
 
 
+class MaxKGATAttentionHeadsFunction(Function):
+    """The attention aggregation of H GAT heads with the softmax inside the walk:
+    apply(graph_indptr, graph_indices, s_dst [H, V], s_src [H, V], topk_values [V, k],
+    topk_indices [V, k], dim_origin, negative_slope) -> [H, V, dim_origin].
+
+    The forward is one maxk_cuda_kernels.gat_attention_heads call.  It saves the graph, the
+    scores, the CBSR and the two row statistics [H, V] -- no tensor of H * E elements.  The
+    backward rebuilds the coefficients with gat_edge_alpha_heads as a transient, runs the
+    stored path's backward on them (edge_weight_grad_heads, gat_edge_softmax_heads_backward,
+    the feature gradient on the route heads_backward_route gives) and drops them."""
+
+    @staticmethod
+    def forward(ctx, graph_indptr, graph_indices, s_dst, s_src, topk_values, topk_indices,
+                dim_origin, negative_slope):
+        _require_kernels()
+        indptr, indices = _i32(graph_indptr), _i32(graph_indices)
+        vals = _f32_act(topk_values)
+        sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
+        sel = sel.contiguous()
+        sd, ss = _f32_act(s_dst), _f32_act(s_src)
+        out, row_max, row_sum = maxk_cuda_kernels.gat_attention_heads(
+            indptr, indices, sd, ss, vals, sel, int(dim_origin), float(negative_slope))
+        V, k = vals.shape
+        ctx.bwd_mode = maxk_cuda_kernels.graph_only_mode(k, indices.numel(), V)
+        ctx.slope = float(negative_slope)
+        ctx.dtypes = (s_dst.dtype, s_src.dtype)
+        ctx.save_for_backward(indptr, indices, sd, ss, vals, sel, row_max, row_sum)
+        ctx.mark_non_differentiable(row_max, row_sum)
+        return out, row_max, row_sum
+
+    @staticmethod
+    def backward(ctx, grad_output, _grad_max, _grad_sum):
+        indptr, indices, sd, ss, vals, sel, row_max, row_sum = ctx.saved_tensors
+        g = grad_output.contiguous()
+        if g.dtype != torch.float32:
+            g = g.float()
+        H = sd.shape[0]
+        need_s = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        grad_sd = grad_ss = grad_tv = None
+        alpha = maxk_cuda_kernels.gat_edge_alpha_heads(indptr, indices, sd, ss, row_max, row_sum,
+                                                       ctx.slope)
+        if need_s:
+            grad_w = maxk_cuda_kernels.edge_weight_grad_heads(indptr, indices, vals, sel, g)
+            grad_sd, grad_ss = maxk_cuda_kernels.gat_edge_softmax_heads_backward(
+                indptr, indices, sd, ss, alpha, grad_w, ctx.slope)
+            del grad_w
+            grad_sd, grad_ss = grad_sd.to(ctx.dtypes[0]), grad_ss.to(ctx.dtypes[1])
+        if ctx.needs_input_grad[4] and maxk_cuda_kernels.heads_backward_route(
+                sel.shape[1], indices.numel(), sel.shape[0], indptr.numel() - 1, H) == "heads":
+            grad_tv = maxk_cuda_kernels.sspmm_backward_heads(indptr, indices, alpha, g, sel)
+        elif ctx.needs_input_grad[4]:
+            for h in range(H):  # accumulated in head order
+                part = maxk_cuda_kernels.sspmm_backward(indptr, indices, alpha[h], g[h], sel,
+                                                        mode=ctx.bwd_mode)
+                grad_tv = part if grad_tv is None else grad_tv.add_(part)
+        del alpha
+        return (None, None, grad_sd if ctx.needs_input_grad[2] else None,
+                grad_ss if ctx.needs_input_grad[3] else None, grad_tv, None, None, None)
+
+
+def maxk_gat_attention_heads(graph_indptr, graph_indices, s_dst, s_src, topk_values,
+                             topk_indices, dim_origin, negative_slope=0.2):
+    """[H, V, dim_origin] = sum over a row's edges of softmax(leaky_relu(s_dst[h, row] +
+    s_src[h, col])) * scatter(topk)[col], for the H heads of one CSR graph, without the
+    coefficients [H, E] being stored; gradients for s_dst, s_src and topk_values
+    (MaxKGATAttentionHeadsFunction)."""
+    _require_kernels()
+    return MaxKGATAttentionHeadsFunction.apply(graph_indptr, graph_indices, s_dst, s_src,
+                                               topk_values, topk_indices, dim_origin,
+                                               negative_slope)[0]
+
+
 class MaxKSpmmWrapper:
     """Holds the warp4 metadata of one graph (maxk_spgemm_function.py:214-267)."""
 

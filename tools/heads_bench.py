@@ -22,6 +22,15 @@ within every iteration so all of them see the same clocks and cache state:
   layer_heads / layer_calls   MaxKMultiHeadGATConv forward plus backward under
                      MAXK_HEADS_SOFTMAX=heads / =calls, out_feats = D / H       (--pairs layer)
 
+  attention_fwd_fused   mk.gat_attention_heads        one call, no alpha        (--pairs attention)
+  attention_fwd_stored  mk.gat_edge_softmax_heads, then the forward mk.heads_forward_route picks
+                        on the graph (spgemm_forward_heads, or H x spgemm_forward)
+  alpha_fused / alpha_stored   mk.gat_edge_alpha_heads from the statistics against
+                        mk.gat_edge_softmax_heads: what the fused backward pays to rebuild alpha
+  step_fused / step_stored     MaxKMultiHeadGATConv forward plus backward, attention="fused"
+                        against "stored", out_feats = D / H, with torch.cuda.max_memory_allocated
+                        of one step of each
+
 It reports the medians, the ratio heads / calls of each pair, and the run-to-run spread of the
 single-head baselines in this run, (max - min) / median over the iterations: the heads kernel
 counts as faster only where 1 - ratio exceeds that spread.  For the feature gradient it also
@@ -31,6 +40,7 @@ timed.  Writes one JSON file and prints it.
   python tools/heads_bench.py [--graphs reddit:16,products:32] [--heads 4,8] [--iters 20]
                               [--pairs forward,edge_grad,feat_grad]
   python tools/heads_bench.py --pairs softmax,layer --heads 1,2,4,8 --out FILE
+  python tools/heads_bench.py --pairs attention --heads 1,2,4,8 --out FILE
 """
 import argparse
 import json
@@ -254,6 +264,123 @@ def run_layer(name, k, D, H, iters, warmup, seed, dev):
     return r
 
 
+def _fused_ratios(r, s, pairs):
+    """ratio fused / stored of each pair; faster only past the baseline's spread in this run."""
+    for a in pairs:
+        r[f"ratio_{a}_fused_to_stored"] = round(
+            s[f"{a}_fused"]["median_ms"] / s[f"{a}_stored"]["median_ms"], 4)
+        r[f"{a}_fused_faster"] = bool(
+            1.0 - r[f"ratio_{a}_fused_to_stored"] > s[f"{a}_stored"]["spread"])
+
+
+def run_attention(name, k, D, H, iters, warmup, seed, dev, slope=0.2):
+    """mk.gat_attention_heads against the softmax and the forward it replaces,
+    mk.gat_edge_alpha_heads against the softmax it replaces in the backward, and the layer's
+    training step under attention="fused" against "stored", alternating inside every
+    iteration; the peak memory of one step of each."""
+    import maxk_layers as ML
+    V = bench.maxk_graph.PRESETS[name]["V"]
+    row_ptr, col = _graph(name, seed, dev)
+    E = col.numel()
+    gen = torch.Generator(device=dev).manual_seed(654)
+    sd = torch.randn(H, V, generator=gen, device=dev)
+    ss = torch.randn(H, V, generator=gen, device=dev)
+    cv, ci = mk.topk_cbsr(torch.rand(V, D, generator=gen, device=dev), k)
+    route = mk.heads_forward_route(V, E)
+    y_f, y_s = torch.empty(H, V, D, device=dev), torch.empty(H, V, D, device=dev)
+    w = torch.empty(H, E, device=dev)
+    w2 = torch.empty(H, E, device=dev)
+    stats = []
+
+    def fwd_fused():
+        stats[:] = mk.gat_attention_heads(row_ptr, col, sd, ss, cv, ci, D, slope, out=y_f,
+                                          validate=False)[1:]
+
+    def fwd_stored():
+        mk.gat_edge_softmax_heads(row_ptr, col, sd, ss, slope, out=w, validate=False)
+        if route == "heads":
+            mk.spgemm_forward_heads(row_ptr, col, w, cv, ci, D, out=y_s, validate=False)
+        else:
+            for h in range(H):
+                mk.spgemm_forward(row_ptr, col, w[h], cv, ci, D, out=y_s[h], validate=False)
+
+    def alpha_fused():
+        mk.gat_edge_alpha_heads(row_ptr, col, sd, ss, stats[0], stats[1], slope, out=w2,
+                                validate=False)
+
+    def alpha_stored():
+        mk.gat_edge_softmax_heads(row_ptr, col, sd, ss, slope, out=w, validate=False)
+
+    ops = (("attention_fwd_fused", fwd_fused), ("attention_fwd_stored", fwd_stored),
+           ("alpha_fused", alpha_fused), ("alpha_stored", alpha_stored))
+    mk.gat_attention_heads(row_ptr, col, sd, ss, cv, ci, D, slope, out=y_f, validate=True)
+    for _ in range(warmup):
+        for _, fn in ops:
+            fn()
+    torch.cuda.synchronize()
+    ts = {n: [] for n, _ in ops}
+    for _ in range(iters):
+        for n, fn in ops:
+            ts[n].append(timed(fn))
+    s = {n: summary(t) for n, t in ts.items()}
+    r = dict(kind="attention", graph=name, V=V, E=E, D=D, k=k, H=H, stored_forward_route=route,
+             **s)
+    r["out_max_diff_over_max"] = float((y_f - y_s).abs().max() / y_s.abs().max())
+    r["alpha_max_abs_diff"] = float((w2 - w).abs().max())
+    r["workspace_bytes_fused"] = int(mk._lib().maxk_gat_attention_heads_workspace_size(
+        V, V, E, D, k, H, 0))
+    r["alpha_bytes"] = 4 * H * E
+    del y_f, y_s, w, w2
+    stats.clear()
+    torch.cuda.empty_cache()
+
+    graph = ML.CSRGraph(row_ptr, col)
+    torch.manual_seed(7)
+    conv = ML.MaxKMultiHeadGATConv(D, D // H, H).to(dev)
+    xs, vals, idx = ML.maxk(torch.rand(V, D, device=dev), k)
+    xs = xs.detach().requires_grad_(True)
+    vals = vals.detach().requires_grad_(True)
+    mk.transpose_plan(col, V)
+
+    def step(mode):
+        conv.attention = mode
+        conv.zero_grad(set_to_none=True)
+        xs.grad = vals.grad = None
+        conv(graph, xs, vals, idx).sum().backward()
+
+    modes = ("fused", "stored")
+    saved = os.environ.pop("MAXK_HEADS_ATTN", None)
+    try:
+        for _ in range(warmup):
+            for mode in modes:
+                step(mode)
+        torch.cuda.synchronize()
+        tl = {mode: [] for mode in modes}
+        for _ in range(iters):
+            for mode in modes:
+                tl[mode].append(timed(lambda: step(mode)))
+        for mode in modes:  # the peak of one step, the other mode's buffers released
+            conv.zero_grad(set_to_none=True)
+            xs.grad = vals.grad = None
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            step(mode)
+            torch.cuda.synchronize()
+            r[f"step_{mode}_peak_bytes"] = int(torch.cuda.max_memory_allocated())
+            r[f"step_{mode}_peak_over_resident_bytes"] = int(torch.cuda.max_memory_allocated()
+                                                             - base)
+    finally:
+        if saved is not None:
+            os.environ["MAXK_HEADS_ATTN"] = saved
+    sl = {f"step_{mode}": summary(t) for mode, t in tl.items()}
+    r.update(sl)
+    s.update(sl)
+    _fused_ratios(r, s, ("attention_fwd", "alpha", "step"))
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--graphs", default="reddit:16,products:32")
@@ -279,6 +406,9 @@ def main():
                               pairs))
             if "softmax" in asked:
                 rs.append(run_softmax(name, H, args.iters, args.warmup, args.seed, dev))
+            if "attention" in asked:
+                rs.append(run_attention(name, int(k), args.dim, H, args.iters, args.warmup,
+                                        args.seed, dev))
             if "layer" in asked and H >= 2:
                 rs.append(run_layer(name, int(k), args.dim, H, args.iters, args.warmup,
                                     args.seed, dev))
