@@ -451,6 +451,72 @@ int maxk_gat_edge_alpha_heads(const int32_t *row_ptr, const int32_t *col_idx, co
                               size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Fused backward of maxk_gat_attention_heads: the three gradients from one walk of the graph,
+ *   alpha_he = exp(l_he - row_max[h,r]) / row_sum[h,r]           (as maxk_gat_edge_alpha_heads)
+ *   ga_he    = sum_l cbsr_val[c,l] * grad_out[h, r, cbsr_idx[c,l]]
+ *   t_hr     = sum_{j : out[h,r,j] != 0} out[h,r,j] * grad_out[h,r,j]
+ *   gz_he    = alpha_he * (ga_he - t_hr) * (z_he > 0 ? 1 : negative_slope),  z = s_dst + s_src
+ *   grad_s_dst[h,r] = sum_{e in r} gz_he       grad_s_src[h,c] = sum_{e: col = c} gz_he
+ *   grad_cbsr[c,l]  = sum_h sum_{e -> c} alpha_he * grad_out[h, r, cbsr_idx[c,l]]
+ * -- what maxk_gat_edge_alpha_heads, maxk_edge_weight_grad_heads,
+ * maxk_gat_edge_softmax_heads_backward and maxk_sspmm_backward_heads compute in four walks, with
+ * no tensor of num_heads * num_e elements in an input, an output or the workspace beside the
+ * edge-major gz [num_e, HP] the column sums read.  out, row_max and row_sum are what the forward
+ * returned; t, the softmax backward's sum over the row of alpha * ga, is the dot product of the
+ * two dense rows out[h,r,:] and grad_out[h,r,:], which every work item forms for itself, so a
+ * row cut over items is walked once.  The terms with out == 0 are skipped: the forward stores
+ * an exact 0 in every column no edge of the row selects, and a NaN or Inf of grad_out there
+ * reaches nothing (the rule of maxk_edge_weight_grad_heads).
+ * col_ptr / csc_eid: the graph's maxk_transpose_plan.  grad_s_dst [num_heads, num_rows],
+ *   grad_s_src [num_heads, num_cols] (summed in CSC slot order) and grad_cbsr [num_cols, dim_k]
+ *   (the heads summed per edge in head order, the edges in CSC slot order).  The reference has no
+ *   counterpart.
+ * Per edge the walk loads col_idx once, one packed record (value and selector) and one score
+ *   vector; alpha and gz are computed once per edge and head.  No global and no LDS atomics.
+ * Shapes: any 1 <= dim_k <= dim_origin <= 256 (dim_k % 4 != 0, odd dim_origin, dim_k > 64),
+ *   1 <= num_heads <= MAXK_MAX_HEADS, any value, one head included; num_rows != num_cols
+ *   allowed; num_e == 0 writes zeros to all three outputs; a table past 2^24 columns or 4 GiB
+ *   of packed records is rejected with MAXK_ERR_INVALID.
+ * Writes: every element of the three outputs.  A row without edges, a column no edge reads and
+ *   a slot whose selector is >= dim_origin give an exact 0; a repeated selector's slots each
+ *   receive the column's gradient.
+ * Numerics (tests/gat_attention_bwd_ref.py): alpha within the edge softmax's bound, ga within
+ *   the edge gradient's, t within (n_t + 8) u sum|out g| plus the error of `out` carried through
+ *   grad_out; gz the product bound of the three; the sums the sum bounds.  The one difference
+ *   from the stored path: there t is summed over the row's edges, here over its columns, so a
+ *   row of a single edge gives gz within the bound, not the exact 0 of ga - ga.
+ * Non-finite values follow the IEEE evaluation of the formulas: a NaN in s_src[h, c] reaches
+ *   head h's grad_s_dst rows that read c, the grad_s_src columns those rows read and grad_cbsr
+ *   of those columns; a -Inf logit gives gz = 0; a NaN of grad_out in a column the row does not
+ *   select reaches nothing.
+ * Bitwise repeatable for equal arguments whatever the workspace held (every sum's order is
+ *   fixed by the graph, chunk_edges, dim_k and num_heads); head h's slices of grad_s_dst and
+ *   grad_s_src do not depend, bitwise, on the other heads' scores (grad_cbsr sums the heads).
+ * Memory, as the top comment: the workspace (contribution rows T [num_e + 1, dim_k] and the
+ *   phase-2 slabs, the packed records, ss_t [num_cols, HP], gz [num_e, HP], the row and column
+ *   slots x num_heads) is exactly the queried size, 256-B aligned, and may hold anything; a
+ *   shorter one is rejected ("workspace too small") on the host before any launch; nothing is
+ *   written outside the outputs and the workspace, inputs are never written; no allocation, copy
+ *   or synchronisation.  The size is non-decreasing in num_e.
+ * Argument errors (num_heads outside [1, MAXK_MAX_HEADS], a null pointer, negative sizes,
+ *   negative_slope outside [0, 1] or NaN, k / D range): MAXK_ERR_INVALID with a message naming
+ *   the argument, before any launch.
+ * chunk_edges: tokens per wavefront work item of every walk, 0 = each walk's auto rule.
+ * ------------------------------------------------------------------------- */
+size_t maxk_gat_attention_heads_backward_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                        int64_t num_e, int32_t dim_origin,
+                                                        int32_t dim_k, int32_t num_heads,
+                                                        int32_t chunk_edges);
+int maxk_gat_attention_heads_backward(
+    const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
+    const int32_t *csc_eid, const float *s_dst, const float *s_src, float negative_slope,
+    const float *cbsr_val, const uint8_t *cbsr_idx, const float *out, const float *row_max,
+    const float *row_sum, const float *grad_out, float *grad_s_dst, float *grad_s_src,
+    float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+    int32_t dim_k, int32_t num_heads, int32_t chunk_edges, void *workspace,
+    size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Backward outer-product sampled SpMM (SSpMM):
  *   grad_cbsr[c,l] = sum_{e=(r->c)} edge_val[e] * grad_out[r, cbsr_idx[c,l]] / row_div[r]
  *                  = (A^T diag(1/row_div) G)[c, cbsr_idx[c,l]]     (from the CSR of A)

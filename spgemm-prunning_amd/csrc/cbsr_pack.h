@@ -231,6 +231,19 @@ inline int fwd_chunk(int64_t num_rows, int64_t num_e, int32_t chunk, int residen
     return (int)fwd_long_rows(num_rows, num_e, c < 64 ? 64 : (c > 256 ? 256 : c), resident);
 }
 
+// Capacity, in items, of what a walk sized by fwd_chunk keeps per item (slabs, slots): at least
+// the item count and non-decreasing in the token count, which the item count of fwd_chunk's auto
+// rule is not (one token more can make the items one token longer and fewer).  The auto rule's
+// items hold at least 64 tokens, and at least tokens / (256 items per CU) until they reach 2048:
+// at most min(tokens / 64, 256 per CU) items below that size and tokens / 2048 at it.
+inline int64_t item_cap(int64_t tokens, int chunk, int n_items) {
+    if (chunk > 0) return n_items;
+    const int64_t a = ceil_div(tokens, 64), k = device_cus() * 256;
+    const int64_t lo = a < k ? a : k, hi = ceil_div(tokens, 2048);
+    const int64_t cap = lo > hi ? lo : hi;
+    return cap > n_items ? cap : n_items;
+}
+
 // LDS row stride per copy: D padded to 16 B, plus one 16-B group holding the
 // trash column (index DS-1, never read by the flush).
 inline int copy_stride(int D) { return ((D + 3) / 4) * 4 + 4; }

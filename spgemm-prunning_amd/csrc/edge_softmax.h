@@ -1,6 +1,7 @@
 // The device helpers and host-side layouts the edge softmax kernels share: edge_softmax.hip (one
 // head) and edge_softmax_heads.hip (H heads over one walk).  The scheme is described at the top
-// of edge_softmax.hip.
+// of edge_softmax.hip.  The last section (H heads) also serves the fused attention's two files,
+// gat_attention_heads.hip and gat_attention_heads_bwd.hip.
 #pragma once
 
 #include <cmath>
@@ -595,8 +596,279 @@ int check_workspace(const void *workspace, size_t bytes, size_t need) {
     MAXK_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-B aligned");
     return MAXK_OK;
 }
-bool sizes_ok(int64_t num_rows, int64_t num_cols, int64_t num_e) {
+inline bool sizes_ok(int64_t num_rows, int64_t num_cols, int64_t num_e) {
     return num_rows >= 0 && num_cols >= 0 && num_e >= 0;
+}
+
+// ---- H heads: what edge_softmax_heads.hip, gat_attention_heads.hip and the fused attention
+// backward (gat_attention_heads_bwd.hip) share --------------------------------------------------
+// The scores interleaved to ss_t [C, HP], the slots of H heads with their merge, and the column
+// sums over gzT [E, HP] through the CSC.  Each translation unit instantiates what it launches.
+
+template <int HP>
+struct alignas(4 * HP) VecF {
+    float v[HP];
+};
+
+__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : slope * v; }
+
+// Slots of H heads: one row array, head h's partials at a / b + h * stride.
+struct SlotsH {
+    int32_t *__restrict__ row;
+    float *__restrict__ a;
+    float *__restrict__ b;
+    int64_t stride;
+    __device__ __forceinline__ Slots head(int h) const {
+        return Slots{row, a + h * stride, b + h * stride};
+    }
+};
+
+template <int HP>
+struct TailH {
+    int row;
+    float a[HP], b[HP];
+    __device__ __forceinline__ TailH() : row(-1) {
+#pragma unroll
+        for (int h = 0; h < HP; ++h) a[h] = b[h] = 0.f;
+    }
+};
+
+template <int HP>
+__device__ __forceinline__ void tail_from_group(TailH<HP> &t, int crow, const float (&ca)[HP],
+                                                const float (&cb)[HP]) {
+    const uint64_t m = __ballot(crow >= 0);
+    if (!m) return;
+    const int src = __builtin_ctzll(m);
+    t.row = __shfl(crow, src);
+#pragma unroll
+    for (int h = 0; h < HP; ++h) {
+        t.a[h] = __shfl(ca[h], src);
+        t.b[h] = __shfl(cb[h], src);
+    }
+}
+
+template <int HP>
+__device__ __forceinline__ void store_slots(const SlotsH &sl, int H, int item,
+                                            const TailH<HP> &head, const TailH<HP> &tail,
+                                            int lane) {
+    if (lane != 0) return;
+    sl.row[2 * item] = head.row;
+    sl.row[2 * item + 1] = tail.row;
+#pragma unroll
+    for (int h = 0; h < HP; ++h) {
+        if (h < H) {
+            const Slots s = sl.head(h);
+            s.a[2 * item] = head.a[h];
+            s.b[2 * item] = head.b[h];
+            s.a[2 * item + 1] = tail.a[h];
+            s.b[2 * item + 1] = tail.b[h];
+        }
+    }
+}
+
+// The interleave pre-pass: ss_t[c] = the HP scores of column c (pad heads 0).
+template <int HP>
+__global__ __launch_bounds__(kBlock) void esmh_interleave_kernel(
+    const float *__restrict__ s_src, VecF<HP> *__restrict__ ss_t, int H, int64_t num_cols) {
+    const int64_t c = blockIdx.x * (int64_t)kBlock + threadIdx.x;
+    if (c >= num_cols) return;
+    VecF<HP> x;
+#pragma unroll
+    for (int h = 0; h < HP; ++h) x.v[h] = h < H ? s_src[h * num_cols + c] : 0.f;
+    ss_t[c] = x;
+}
+
+// acc[h] = the sum over the CSC slots [0, n) of gzT[eid[i]].v[h].
+template <int HP>
+__device__ __forceinline__ void piece_gather(const VecF<HP> *__restrict__ gzT,
+                                             const int32_t *__restrict__ eid, int H, int n,
+                                             int lane, float (&acc)[HP]) {
+#pragma unroll
+    for (int h = 0; h < HP; ++h) acc[h] = 0.f;
+    for (int base = 0; base < n; base += kWave * kU) {
+        VecF<HP> g[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int i = base + u * kWave + lane;
+#pragma unroll
+            for (int h = 0; h < HP; ++h) g[u].v[h] = 0.f;
+            if (i < n) g[u] = gzT[(uint32_t)eid[i]];
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u)
+#pragma unroll
+            for (int h = 0; h < HP; ++h) acc[h] += g[u].v[h];
+    }
+#pragma unroll
+    for (int h = 0; h < HP; ++h)
+        if (h < H) acc[h] = lane_tree<kWave, Sum>(acc[h]);
+}
+
+// A whole column writes grad_s_src, 0 for an unread one; a cut one leaves its partials in `tail`.
+template <int HP>
+__device__ __forceinline__ int short_cols_sum(const int32_t *__restrict__ col_ptr,
+                                              const int32_t *__restrict__ eid,
+                                              const VecF<HP> *__restrict__ gzT,
+                                              float *__restrict__ grad_s_src, int H,
+                                              int64_t num_cols, int first, int64_t d1, int lane,
+                                              TailH<HP> &tail) {
+    const int g = lane / kLR, j = lane % kLR;
+    RowHandout<CutAtEnd> ho(col_ptr, (int)num_cols, first, d1, kShort, lane);
+    int crow = -1;
+    float ca[HP], zero[HP];
+#pragma unroll
+    for (int h = 0; h < HP; ++h) ca[h] = zero[h] = 0.f;
+    for (;;) {
+        int row = -1, b = 0, e = 0;
+        ho.template assign<1>(true, kNG, kLR, g, lane, [&](int r, int rb, int re) {
+            row = r;
+            b = rb;
+            e = re;
+        });
+        if (!__ballot(row >= 0)) break;
+        const bool has = row >= 0;
+        const int n = has ? e - b : 0;  // this lane's row piece: [b, b + n)
+        const int full = has ? col_ptr[row + 1] : 0;
+        const bool cut = has && e < full;
+        float acc[HP];
+#pragma unroll
+        for (int h = 0; h < HP; ++h) acc[h] = 0.f;
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            const int o = j + kLR * u;
+            VecF<HP> x;
+#pragma unroll
+            for (int h = 0; h < HP; ++h) x.v[h] = 0.f;
+            if (o < n) x = gzT[(uint32_t)eid[b + o]];
+#pragma unroll
+            for (int h = 0; h < HP; ++h) acc[h] += x.v[h];
+        }
+#pragma unroll
+        for (int h = 0; h < HP; ++h) {
+            if (h < H) {
+                acc[h] = lane_tree<kLR, Sum>(acc[h]);
+                if (has && !cut && j == 0) grad_s_src[h * num_cols + row] = acc[h];
+                if (cut && e > b) ca[h] = acc[h];
+            }
+        }
+        if (cut && e > b) crow = row;
+    }
+    tail_from_group<HP>(tail, crow, ca, zero);
+    return ho.next;
+}
+
+// The merge above, one head per blockIdx.y.  VAL_B: the partial sums are in b.
+template <int MODE, bool VAL_B>
+__global__ __launch_bounds__(kBlock) void esmh_merge_kernel(SlotsH slh, float *__restrict__ out,
+                                                            int64_t out_stride, int n_slots) {
+    const Slots sl = slh.head((int)blockIdx.y);
+    merge_slots<MODE>(sl, VAL_B ? sl.b : sl.a, out ? out + blockIdx.y * out_stride : nullptr,
+                      n_slots);
+}
+
+// grad_s_src[h, c] = the sum of gzT[.].v[h] over column c's CSC slots, in slot order; a cut
+// column leaves its partials in the slots.
+template <int HP>
+__global__ __launch_bounds__(kBlock) void esmh_colsum_kernel(
+    const int32_t *__restrict__ col_ptr, const int32_t *__restrict__ eid,
+    const VecF<HP> *__restrict__ gzT, float *__restrict__ grad_s_src, SlotsH sl, int H,
+    int64_t num_cols, int64_t num_e, int chunk, int n_items) {
+    const int item = item_of_wave(n_items);
+    if (item < 0) return;
+    const int lane = lane_id();
+    const int nc = (int)num_cols;
+    const ItemRange it = item_range(col_ptr, nc, num_e, item, chunk);
+    TailH<HP> head, tail;
+    if (it.r > 0) {
+        const RowPiece p = cont_piece(CutAtEnd{}, it.p_lo, it.d1, it.r, col_ptr[it.r]);
+        if (p.sb < p.se) {
+            head.row = it.r - 1;
+            piece_gather<HP>(gzT, eid + p.sb, H, (int)(p.se - p.sb), lane, head.a);
+        }
+    }
+    int c = it.r;
+    while (c < nc) {
+        c = short_cols_sum<HP>(col_ptr, eid, gzT, grad_s_src, H, num_cols, c, it.d1, lane, tail);
+        if (c >= nc) break;
+        const int64_t cb = col_ptr[c];
+        if (!row_owned(it.d1, c, cb)) break;
+        const int64_t ce = col_ptr[c + 1];
+        const RowPiece p = row_piece(CutAtEnd{}, it.d1, c, cb, ce);
+        const int n = (int)(p.se - p.sb);
+        if (n > 0) {
+            float acc[HP];
+            piece_gather<HP>(gzT, eid + p.sb, H, n, lane, acc);
+            if (p.se == ce) {
+#pragma unroll
+                for (int h = 0; h < HP; ++h)
+                    if (h < H && lane == 0) grad_s_src[h * num_cols + c] = acc[h];
+            } else {
+                tail.row = c;
+#pragma unroll
+                for (int h = 0; h < HP; ++h) tail.a[h] = acc[h];
+            }
+        } else if (ce == cb && lane == 0) {
+#pragma unroll
+            for (int h = 0; h < HP; ++h)
+                if (h < H) grad_s_src[h * num_cols + c] = 0.f;
+        }
+        ++c;
+    }
+    store_slots<HP>(sl, H, item, head, tail, lane);
+}
+
+// Heads padded to a vector of 2, 4 or 8 scores.
+inline int hp_of(int H) { return H <= 2 ? 2 : H <= 4 ? 4 : 8; }
+
+// Slots of H heads over n rows (or columns): [row | a x H | b x H], each part the single-head
+// size, so head h's a and b are arrays the single-head merge takes.
+struct SlotLayoutH {
+    int chunk, n_items;
+    size_t row_off, a_off, b_off, end;
+    int64_t stride;  // floats between two heads' partials
+};
+inline SlotLayoutH slot_layout_h(int64_t n, int64_t num_e, int chunk, int H, size_t base) {
+    const SlotLayout one = slot_layout(n, num_e, chunk, 0);
+    const size_t bytes = one.a_off;  // one part
+    SlotLayoutH L{};
+    L.chunk = one.chunk;
+    L.n_items = one.n_items;
+    L.row_off = base;
+    L.a_off = L.row_off + bytes;
+    L.b_off = L.a_off + (size_t)H * bytes;
+    L.end = L.b_off + (size_t)H * bytes;
+    L.stride = (int64_t)(bytes / sizeof(float));
+    return L;
+}
+inline SlotsH slots_at(void *ws, const SlotLayoutH &L) {
+    uint8_t *p = reinterpret_cast<uint8_t *>(ws);
+    return SlotsH{reinterpret_cast<int32_t *>(p + L.row_off),
+                  reinterpret_cast<float *>(p + L.a_off), reinterpret_cast<float *>(p + L.b_off),
+                  L.stride};
+}
+
+inline dim3 with_heads(dim3 g, int H) { return dim3(g.x, (unsigned)H); }
+
+inline int check_heads(int32_t num_heads) {
+    MAXK_REQUIRE(num_heads >= 1 && num_heads <= MAXK_MAX_HEADS,
+                 "num_heads must be in [1,%d], got %d", MAXK_MAX_HEADS, num_heads);
+    return MAXK_OK;
+}
+
+// The column sums of the heads' backward over gzT [E, HP]: esmh_colsum_kernel and the merge of
+// the cut columns, into grad_s_src [H, num_cols] (every element written).
+template <int HP>
+int launch_heads_colsum(const int32_t *col_ptr, const int32_t *csc_eid, const VecF<HP> *gzT,
+                        float *grad_s_src, void *workspace, const SlotLayoutH &C, int H,
+                        int64_t num_cols, int64_t num_e, hipStream_t s) {
+    const SlotsH csl = slots_at(workspace, C);
+    hipLaunchKernelGGL(esmh_colsum_kernel<HP>, item_grid(C.n_items), dim3(kBlock), 0, s, col_ptr,
+                       csc_eid, gzT, grad_s_src, csl, H, num_cols, num_e, C.chunk, C.n_items);
+    MAXK_LAUNCHED("esmh_colsum_kernel");
+    hipLaunchKernelGGL((esmh_merge_kernel<kMergeOut, false>), with_heads(slot_grid(C.n_items), H),
+                       dim3(kBlock), 0, s, csl, grad_s_src, num_cols, 2 * C.n_items);
+    MAXK_LAUNCHED("esmh_merge_kernel");
+    return MAXK_OK;
 }
 
 }  // namespace

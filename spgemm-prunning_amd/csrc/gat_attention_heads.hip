@@ -48,13 +48,6 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int HP>
-struct alignas(4 * HP) VecF {
-    float v[HP];
-};
-
-__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : slope * v; }
-
 __device__ __forceinline__ float uniform(float x) {
     return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x)));
 }
@@ -449,26 +442,11 @@ __global__ __launch_bounds__(kBlock) void gath_alpha_kernel(
 // A piece is addressed through a descriptor of 4 * n bytes with 32-bit offsets.
 constexpr int kAttnMaxChunk = 1 << 24;
 
-int hp_of(int H) { return H <= 2 ? 2 : H <= 4 ? 4 : 8; }
-
 struct AttnLayout {
     int chunk, n_items, RS, DS, kg, hc, hp;
     bool wide;
     size_t ss_off, slab_off, m_off, z_off, row_off, total;
 };
-
-// Slab capacity, in items: at least the item count and non-decreasing in the token count, which
-// the item count of fwd_chunk's auto rule is not (one token more can make the items one token
-// longer and fewer).  The auto rule's items hold at least 64 tokens, and at least
-// tokens / (256 items per CU) until they reach 2048: at most min(tokens / 64, 256 per CU) items
-// below that size and tokens / 2048 at it.
-int64_t item_cap(int64_t tokens, int chunk, int n_items) {
-    if (chunk > 0) return n_items;
-    const int64_t a = ceil_div(tokens, 64), k = device_cus() * 256;
-    const int64_t lo = a < k ? a : k, hi = ceil_div(tokens, 2048);
-    const int64_t cap = lo > hi ? lo : hi;
-    return cap > n_items ? cap : n_items;
-}
 
 AttnLayout attn_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, int k, int H,
                        int chunk) {
@@ -498,12 +476,6 @@ AttnLayout attn_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D,
     L.row_off = L.z_off + stat;
     L.total = L.row_off + al256((size_t)cap * sizeof(int32_t));
     return L;
-}
-
-int check_heads(int32_t num_heads) {
-    MAXK_REQUIRE(num_heads >= 1 && num_heads <= MAXK_MAX_HEADS,
-                 "num_heads must be in [1,%d], got %d", MAXK_MAX_HEADS, num_heads);
-    return MAXK_OK;
 }
 
 template <int HP>

@@ -36,4 +36,15 @@ inline int check_common(int64_t num_rows, int64_t num_cols, int64_t num_e, int32
     return MAXK_OK;
 }
 
+// The csc phase 2 on its own (sspmm_push.hip), for a phase 1 that lives in another file (the
+// fused attention backward): `ws` starts with the contribution rows T [num_e + 1, k] in CSR edge
+// order (the last one the dummy row of masked lanes), which the caller has written; the rest of
+// it is phase 2's slabs.  csc_sum_workspace_size: the bytes of `ws`, non-decreasing in num_e
+// (the item count of the auto item size is not, so the slabs are sized by its largest).
+// csc_sum_rows: grad_cbsr[c, :] = the sum of T[csc_eid[t], :] over column c's CSC slots t, in
+// slot order, every row written; launches only.
+size_t csc_sum_workspace_size(int64_t num_cols, int64_t num_e, int k, int chunk);
+int csc_sum_rows(hipStream_t s, const int32_t *col_ptr, const int32_t *csc_eid, void *ws,
+                 float *grad_cbsr, int64_t num_cols, int64_t num_e, int k, int chunk);
+
 }  // namespace maxk

@@ -1060,6 +1060,26 @@ __global__ __launch_bounds__(kBlock) void edge_sel_kernel(const int32_t *__restr
     }
 }
 }  // namespace
+
+size_t csc_sum_workspace_size(int64_t num_cols, int64_t num_e, int k, int chunk) {
+    const CscLayout L = csc_layout(num_cols, num_e, k, chunk);
+    if (chunk > 0) return L.total;
+    // bwd_chunk's items hold at least 256 tokens, and at least tokens / (its item target) until
+    // they reach 2048
+    const int64_t tokens = num_cols + num_e, aim = device_cus() * 32 * MAXK_P2_ITEMS;
+    const int64_t a = ceil_div(tokens, 256), lo = a < aim ? a : aim, hi = ceil_div(tokens, 2048);
+    int64_t cap = lo > hi ? lo : hi;
+    if (cap < L.n_items) cap = L.n_items;
+    return L.t_bytes + al256((size_t)cap * k * sizeof(float)) +
+           al256((size_t)cap * sizeof(int32_t));
+}
+
+int csc_sum_rows(hipStream_t s, const int32_t *col_ptr, const int32_t *csc_eid, void *ws,
+                 float *grad_cbsr, int64_t num_cols, int64_t num_e, int k, int chunk) {
+    return launch_csc_sum(s, csc_layout(num_cols, num_e, k, chunk), col_ptr, csc_eid,
+                          reinterpret_cast<char *>(ws), grad_cbsr, num_cols, num_e, k);
+}
+
 }  // namespace maxk
 
 extern "C" int maxk_sspmm_backward_csc(const int32_t *row_ptr, const int32_t *col_idx,

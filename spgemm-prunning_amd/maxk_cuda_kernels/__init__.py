@@ -51,6 +51,7 @@ __all__ = [
     "sspmm_backward_heads", "heads_backward_route",
     "gat_edge_softmax_heads", "gat_edge_softmax_heads_backward", "heads_softmax_route",
     "gat_attention_heads", "gat_edge_alpha_heads", "heads_attention_route",
+    "gat_attention_heads_backward", "heads_attention_backward_route",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -735,6 +736,73 @@ def heads_attention_route(num_heads: int, num_rows: int, num_e: int) -> Tuple[st
         return forced, forced
     dense = num_e >= HEADS_SPARSE_DEGREE * num_rows
     return ("fused" if dense and num_heads >= 2 else "stored"), "stored"
+
+
+def gat_attention_heads_backward(indptr: torch.Tensor, indices: torch.Tensor,
+                                 s_dst: torch.Tensor, s_src: torch.Tensor,
+                                 cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor,
+                                 out: torch.Tensor, row_max: torch.Tensor, row_sum: torch.Tensor,
+                                 grad_output: torch.Tensor, negative_slope: float = 0.2,
+                                 chunk: int = 0, validate: Optional[bool] = None, plan=None):
+    """(grad_s_dst [H, num_rows], grad_s_src [H, num_cols], grad_cbsr [num_cols, k]) of
+    gat_attention_heads from its three results and the gradient of `out`, in one walk of the
+    graph (maxk_gat_attention_heads_backward): what gat_edge_alpha_heads, edge_weight_grad_heads,
+    gat_edge_softmax_heads_backward and sspmm_backward_heads compute in four, with no [H, E]
+    tensor allocated.  The row sum of the softmax backward is taken as the dot product of
+    out[h, r] and grad_output[h, r], so `out` must be the forward's.  Uses the graph's transpose
+    plan (cached per `indices`, or `plan=` from transpose_plan()).  Bitwise repeatable; the same
+    operand checks as gat_attention_heads."""
+    _need(grad_output, "grad_output", torch.float32)
+    _need(out, "out", torch.float32)
+    if grad_output.dim() != 3 or not 1 <= grad_output.shape[0] <= MAX_HEADS:
+        raise RuntimeError(f"grad_output must be [H, num_rows, dim_origin] with 1 <= H <= "
+                           f"{MAX_HEADS}")
+    D = grad_output.shape[2]
+    H, num_rows, num_cols, E = _gat_heads_operands(indptr, indices, s_dst, s_src)
+    _, cols2, k = _heads_operands(indptr, indices, cbsr_val, cbsr_idx, None, validate, D)
+    if cols2 != num_cols:
+        raise RuntimeError("s_src must be [H, num_cols] with num_cols = input_data.shape[0]")
+    if tuple(grad_output.shape) != (H, num_rows, D) or tuple(out.shape) != (H, num_rows, D):
+        raise RuntimeError("out and grad_output must be [H, num_rows, dim_origin]")
+    _need(row_max, "row_max", torch.float32)
+    _need(row_sum, "row_sum", torch.float32)
+    if tuple(row_max.shape) != (H, num_rows) or tuple(row_sum.shape) != (H, num_rows):
+        raise RuntimeError("row_max and row_sum must be [H, num_rows]")
+    dev = cbsr_val.device
+    col_ptr, csc_eid = plan if plan is not None else transpose_plan(indices, num_cols)
+    g_dst = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
+    g_src = torch.empty(H, num_cols, dtype=torch.float32, device=dev)
+    g_cbsr = torch.empty(num_cols, k, dtype=torch.float32, device=dev)
+    shape = (num_rows, num_cols, E, D, k, H, chunk)
+    _launch_ws(dev, "maxk_gat_attention_heads_backward",
+               "maxk_gat_attention_heads_backward_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(s_dst),
+                _ptr(s_src), float(negative_slope), _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out),
+                _ptr(row_max), _ptr(row_sum), _ptr(grad_output), _ptr(g_dst), _ptr(g_src),
+                _ptr(g_cbsr), *shape))
+    return g_dst, g_src, g_cbsr
+
+
+def heads_attention_backward_route(num_heads: int, num_rows: int, num_e: int) -> str:
+    """How the backward of a fused multi-head attention should run: "fused", one
+    gat_attention_heads_backward call, or "rebuilt", gat_edge_alpha_heads and the stored path's
+    three passes.  Measured against exactly those four calls in the same run
+    (profiles/r16/gat_attention_bwd/), fused / rebuilt at H = 1, 2, 4, 8:
+    Reddit-sized k = 16 0.88, 0.76, 0.66, 0.55; products-sized k = 32 0.96, 0.90, 0.80, 0.66,
+    against spreads of the rebuilt backward of 0.8 to 3.1 % -- a win past the spread at every
+    point, the one-head products-sized one by less than a point -- and the layer's training step
+    0.78 to 0.99 of the step with the rebuilt backward.  So the rule has no threshold and
+    num_rows and num_e do not enter it: "fused" for every head count.  What it costs is memory:
+    `out` [H, V, D] stays alive until this backward has run and T [E, k] and gz [E, HP] are live
+    together, so the step peaks above the rebuilt backward's (16.8 against 14.9 GB Reddit-sized
+    and 67.4 against 48.7 GB products-sized at 8 heads; the stored path: 18.5 and 52.5 GB):
+    "rebuilt" remains the memory-saving option.  MAXK_HEADS_ATTN_BWD=fused|rebuilt forces one.
+    Not wired into a default: MaxKMultiHeadGATConv's `attention_backward` defaults to
+    "rebuilt"."""
+    forced = os.environ.get("MAXK_HEADS_ATTN_BWD", "")
+    if forced in ("fused", "rebuilt"):
+        return forced
+    return "fused"
 
 
 def records_ok(num_rows: int, num_cols: int, num_e: int, dim_origin: int, k: int) -> bool:

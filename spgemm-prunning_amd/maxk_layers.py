@@ -95,12 +95,19 @@ class CSRGraph:
                                  dim, row_div)
 
     def attend_heads(self, topk_values, topk_indices, dim: int, s_dst, s_src,
-                     negative_slope: float = 0.2):
+                     negative_slope: float = 0.2, backward: str = "rebuilt"):
         """[H, V, dim]: the attention aggregation of H GAT heads from their scores s_dst [H, V]
         and s_src [H, V] with the softmax inside the walk (maxk_gat_attention_heads): what
-        gat_edge_softmax_heads followed by aggregate_heads give, without alpha [H, E] stored."""
+        gat_edge_softmax_heads followed by aggregate_heads give, without alpha [H, E] stored.
+        backward: "rebuilt" (alpha as a transient of the backward) or "fused" (one walk, no
+        [H, E] tensor in the backward either); MAXK_HEADS_ATTN_BWD=fused|rebuilt overrides it."""
+        if backward not in ("rebuilt", "fused"):
+            raise ValueError(f'backward must be "rebuilt" or "fused", got {backward!r}')
+        forced = os.environ.get("MAXK_HEADS_ATTN_BWD", "")
+        if forced in ("fused", "rebuilt"):
+            backward = forced
         return maxk_gat_attention_heads(self.indptr, self.indices, s_dst, s_src, topk_values,
-                                        topk_indices, dim, negative_slope)
+                                        topk_indices, dim, negative_slope, backward)
 
 
 class MaxK(Function):
@@ -492,15 +499,22 @@ class MaxKMultiHeadGATConv(nn.Module):
     attention="stored" (the default) keeps alpha [H, E] between forward and backward;
     attention="fused" computes the softmax inside the aggregation walk
     (CSRGraph.attend_heads), keeps the row statistics [H, V] instead and rebuilds alpha as a
-    transient in the backward.  MAXK_HEADS_ATTN=fused|stored overrides the argument."""
+    transient in the backward.  MAXK_HEADS_ATTN=fused|stored overrides the argument.
+    attention_backward="fused" (with the fused attention only; the default is "rebuilt") runs
+    that backward as one walk without alpha (CSRGraph.attend_heads(backward="fused"));
+    MAXK_HEADS_ATTN_BWD=fused|rebuilt overrides the argument."""
 
     def __init__(self, in_feats: int, out_feats: int, num_heads: int,
                  negative_slope: float = 0.2, bias: bool = True, activation=None,
-                 attention: str = "stored"):
+                 attention: str = "stored", attention_backward: str = "rebuilt"):
         super().__init__()
         if attention not in ("stored", "fused"):
             raise ValueError(f'attention must be "stored" or "fused", got {attention!r}')
+        if attention_backward not in ("rebuilt", "fused"):
+            raise ValueError('attention_backward must be "rebuilt" or "fused", got '
+                             f'{attention_backward!r}')
         self.attention = attention
+        self.attention_backward = attention_backward
         if not 1 <= int(num_heads) <= mk.MAX_HEADS:
             raise ValueError(f"num_heads must be in [1, {mk.MAX_HEADS}], got {num_heads}")
         self.in_feats, self.out_feats, self.num_heads = in_feats, out_feats, int(num_heads)
@@ -521,6 +535,13 @@ class MaxKMultiHeadGATConv(nn.Module):
         forced = os.environ.get("MAXK_HEADS_ATTN", "")
         return forced if forced in ("fused", "stored") else self.attention
 
+    def attention_backward_mode(self) -> str:
+        """"fused" or "rebuilt", the backward of the fused attention: MAXK_HEADS_ATTN_BWD when
+        it names one, else the `attention_backward` argument.  Without effect where
+        attention_mode() is "stored"."""
+        forced = os.environ.get("MAXK_HEADS_ATTN_BWD", "")
+        return forced if forced in ("fused", "rebuilt") else self.attention_backward
+
     def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices):
         H, O = self.num_heads, self.out_feats
         W = self.fc.weight.view(H, O, self.in_feats)
@@ -530,7 +551,7 @@ class MaxKMultiHeadGATConv(nn.Module):
         s = (x_sparse @ v).t().contiguous()                               # [2H, V]
         if self.attention_mode() == "fused":
             agg = graph.attend_heads(topk_values, topk_indices, self.in_feats, s[:H], s[H:],
-                                     self.negative_slope)
+                                     self.negative_slope, self.attention_backward_mode())
         else:
             alpha = gat_edge_softmax_heads(graph, s[:H], s[H:], self.negative_slope)
             agg = graph.aggregate_heads(topk_values, topk_indices, self.in_feats, alpha)

@@ -396,12 +396,20 @@ class MaxKGATAttentionHeadsFunction(Function):
     scores, the CBSR and the two row statistics [H, V] -- no tensor of H * E elements.  The
     backward rebuilds the coefficients with gat_edge_alpha_heads as a transient, runs the
     stored path's backward on them (edge_weight_grad_heads, gat_edge_softmax_heads_backward,
-    the feature gradient on the route heads_backward_route gives) and drops them."""
+    the feature gradient on the route heads_backward_route gives) and drops them.
+
+    backward="fused" (a ninth argument; "rebuilt", the above, is the default) saves `out` as
+    well and runs one maxk_cuda_kernels.gat_attention_heads_backward call instead: no tensor of
+    H * E elements in the backward either.  It falls back to the rebuilt backward when not all
+    three gradients are needed, when the table is too large for the entry
+    (maxk_cuda_kernels.HEADS_MAX_COLS) and when MAXK_BWD_MODE forces a backward mode."""
 
     @staticmethod
     def forward(ctx, graph_indptr, graph_indices, s_dst, s_src, topk_values, topk_indices,
-                dim_origin, negative_slope):
+                dim_origin, negative_slope, backward="rebuilt"):
         _require_kernels()
+        if backward not in ("rebuilt", "fused"):
+            raise ValueError(f'backward must be "rebuilt" or "fused", got {backward!r}')
         indptr, indices = _i32(graph_indptr), _i32(graph_indices)
         vals = _f32_act(topk_values)
         sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
@@ -413,19 +421,30 @@ class MaxKGATAttentionHeadsFunction(Function):
         ctx.bwd_mode = maxk_cuda_kernels.graph_only_mode(k, indices.numel(), V)
         ctx.slope = float(negative_slope)
         ctx.dtypes = (s_dst.dtype, s_src.dtype)
-        ctx.save_for_backward(indptr, indices, sd, ss, vals, sel, row_max, row_sum)
+        ctx.fused_bwd = (backward == "fused" and V < maxk_cuda_kernels.HEADS_MAX_COLS
+                         and ctx.bwd_mode is not None)
+        if ctx.fused_bwd:
+            ctx.save_for_backward(indptr, indices, sd, ss, vals, sel, row_max, row_sum, out)
+        else:
+            ctx.save_for_backward(indptr, indices, sd, ss, vals, sel, row_max, row_sum)
         ctx.mark_non_differentiable(row_max, row_sum)
         return out, row_max, row_sum
 
     @staticmethod
     def backward(ctx, grad_output, _grad_max, _grad_sum):
-        indptr, indices, sd, ss, vals, sel, row_max, row_sum = ctx.saved_tensors
+        indptr, indices, sd, ss, vals, sel, row_max, row_sum = ctx.saved_tensors[:8]
         g = grad_output.contiguous()
         if g.dtype != torch.float32:
             g = g.float()
         H = sd.shape[0]
         need_s = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         grad_sd = grad_ss = grad_tv = None
+        if ctx.fused_bwd and all(ctx.needs_input_grad[2:5]):
+            grad_sd, grad_ss, grad_tv = maxk_cuda_kernels.gat_attention_heads_backward(
+                indptr, indices, sd, ss, vals, sel, ctx.saved_tensors[8], row_max, row_sum, g,
+                ctx.slope)
+            return (None, None, grad_sd.to(ctx.dtypes[0]), grad_ss.to(ctx.dtypes[1]), grad_tv,
+                    None, None, None, None)
         alpha = maxk_cuda_kernels.gat_edge_alpha_heads(indptr, indices, sd, ss, row_max, row_sum,
                                                        ctx.slope)
         if need_s:
@@ -444,19 +463,20 @@ class MaxKGATAttentionHeadsFunction(Function):
                 grad_tv = part if grad_tv is None else grad_tv.add_(part)
         del alpha
         return (None, None, grad_sd if ctx.needs_input_grad[2] else None,
-                grad_ss if ctx.needs_input_grad[3] else None, grad_tv, None, None, None)
+                grad_ss if ctx.needs_input_grad[3] else None, grad_tv, None, None, None, None)
 
 
 def maxk_gat_attention_heads(graph_indptr, graph_indices, s_dst, s_src, topk_values,
-                             topk_indices, dim_origin, negative_slope=0.2):
+                             topk_indices, dim_origin, negative_slope=0.2, backward="rebuilt"):
     """[H, V, dim_origin] = sum over a row's edges of softmax(leaky_relu(s_dst[h, row] +
     s_src[h, col])) * scatter(topk)[col], for the H heads of one CSR graph, without the
     coefficients [H, E] being stored; gradients for s_dst, s_src and topk_values
-    (MaxKGATAttentionHeadsFunction)."""
+    (MaxKGATAttentionHeadsFunction).  backward: "rebuilt" (the coefficients as a transient and
+    the stored path's passes) or "fused" (one gat_attention_heads_backward call)."""
     _require_kernels()
     return MaxKGATAttentionHeadsFunction.apply(graph_indptr, graph_indices, s_dst, s_src,
                                                topk_values, topk_indices, dim_origin,
-                                               negative_slope)[0]
+                                               negative_slope, backward)[0]
 
 
 class MaxKSpmmWrapper:

@@ -31,6 +31,14 @@ within every iteration so all of them see the same clocks and cache state:
                         against "stored", out_feats = D / H, with torch.cuda.max_memory_allocated
                         of one step of each
 
+  attention_bwd_fused    mk.gat_attention_heads_backward   one call      (--pairs attention_bwd)
+  attention_bwd_rebuilt  mk.gat_edge_alpha_heads, mk.edge_weight_grad_heads,
+                        mk.gat_edge_softmax_heads_backward and the feature gradient
+                        mk.heads_backward_route picks: the rebuilt backward it replaces
+  step_stored / step_fused_rebuilt / step_fused_fused   the layer's forward plus backward for
+                        attention stored, fused with the rebuilt backward and fused with the
+                        fused backward, with the peak memory of one step of each
+
 It reports the medians, the ratio heads / calls of each pair, and the run-to-run spread of the
 single-head baselines in this run, (max - min) / median over the iterations: the heads kernel
 counts as faster only where 1 - ratio exceeds that spread.  For the feature gradient it also
@@ -381,6 +389,134 @@ def run_attention(name, k, D, H, iters, warmup, seed, dev, slope=0.2):
     return r
 
 
+def run_attention_bwd(name, k, D, H, iters, warmup, seed, dev, slope=0.2):
+    """mk.gat_attention_heads_backward against exactly what it replaces (gat_edge_alpha_heads,
+    edge_weight_grad_heads, gat_edge_softmax_heads_backward and the feature gradient
+    heads_backward_route picks), alternating inside every iteration; then the layer's training
+    step for attention stored, fused with the rebuilt backward and fused with the fused one, and
+    the peak memory of one step of each."""
+    import maxk_layers as ML
+    V = bench.maxk_graph.PRESETS[name]["V"]
+    row_ptr, col = _graph(name, seed, dev)
+    E = col.numel()
+    gen = torch.Generator(device=dev).manual_seed(987)
+    sd = torch.randn(H, V, generator=gen, device=dev)
+    ss = torch.randn(H, V, generator=gen, device=dev)
+    cv, ci = mk.topk_cbsr(torch.rand(V, D, generator=gen, device=dev), k)
+    G = torch.randn(H, V, D, generator=gen, device=dev)
+    out, m, z = mk.gat_attention_heads(row_ptr, col, sd, ss, cv, ci, D, slope, validate=True)
+    plan = mk.transpose_plan(col, V)  # once per graph, as in training: not part of either side
+    route = mk.heads_backward_route(k, E, V, V, H)
+    mode = mk.graph_only_mode(k, E, V)
+    keep = {}
+
+    def bwd_fused():
+        keep["fused"] = mk.gat_attention_heads_backward(row_ptr, col, sd, ss, cv, ci, out, m, z,
+                                                        G, slope, validate=False, plan=plan)
+
+    def bwd_rebuilt():  # MaxKGATAttentionHeadsFunction.backward, route "rebuilt"
+        alpha = mk.gat_edge_alpha_heads(row_ptr, col, sd, ss, m, z, slope, validate=False)
+        gw = mk.edge_weight_grad_heads(row_ptr, col, cv, ci, G, validate=False)
+        g_dst, g_src = mk.gat_edge_softmax_heads_backward(row_ptr, col, sd, ss, alpha, gw, slope,
+                                                          validate=False)
+        del gw
+        if route == "heads":
+            g_tv = mk.sspmm_backward_heads(row_ptr, col, alpha, G, ci, validate=False, plan=plan)
+        else:
+            g_tv = None
+            for h in range(H):
+                part = mk.sspmm_backward(row_ptr, col, alpha[h], G[h], ci, mode=mode,
+                                         validate=False)
+                g_tv = part if g_tv is None else g_tv.add_(part)
+        keep["rebuilt"] = (g_dst, g_src, g_tv)
+
+    ops = (("attention_bwd_fused", bwd_fused), ("attention_bwd_rebuilt", bwd_rebuilt))
+    for _ in range(warmup):
+        for _, fn in ops:
+            fn()
+    torch.cuda.synchronize()
+    ts = {n: [] for n, _ in ops}
+    for _ in range(iters):
+        for n, fn in ops:
+            ts[n].append(timed(fn))
+    s = {n: summary(t) for n, t in ts.items()}
+    r = dict(kind="attention_bwd", graph=name, V=V, E=E, D=D, k=k, H=H,
+             rebuilt_feature_route=route, **s)
+    for what, a, b in zip(("grad_s_dst", "grad_s_src", "grad_cbsr"), keep["fused"],
+                          keep["rebuilt"]):
+        r[f"{what}_max_diff_over_max"] = float((a - b).abs().max() / b.abs().max())
+    r["workspace_bytes_fused"] = int(mk._lib().maxk_gat_attention_heads_backward_workspace_size(
+        V, V, E, D, k, H, 0))
+    r["alpha_bytes"] = 4 * H * E
+    for n, fn in ops:  # the peak of one backward over what is resident before it
+        keep.clear()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        r[f"{n}_peak_over_resident_bytes"] = int(torch.cuda.max_memory_allocated() - base)
+    keep.clear()
+    del out, m, z, G
+    torch.cuda.empty_cache()
+
+    graph = ML.CSRGraph(row_ptr, col)
+    torch.manual_seed(7)
+    conv = ML.MaxKMultiHeadGATConv(D, D // H, H).to(dev)
+    xs, vals, idx = ML.maxk(torch.rand(V, D, device=dev), k)
+    xs = xs.detach().requires_grad_(True)
+    vals = vals.detach().requires_grad_(True)
+    modes = {"stored": ("stored", "rebuilt"), "fused_rebuilt": ("fused", "rebuilt"),
+             "fused_fused": ("fused", "fused")}
+
+    def step(mode):
+        conv.attention, conv.attention_backward = modes[mode]
+        conv.zero_grad(set_to_none=True)
+        xs.grad = vals.grad = None
+        conv(graph, xs, vals, idx).sum().backward()
+
+    saved = {v: os.environ.pop(v, None) for v in ("MAXK_HEADS_ATTN", "MAXK_HEADS_ATTN_BWD")}
+    try:
+        for _ in range(warmup):
+            for mode in modes:
+                step(mode)
+        torch.cuda.synchronize()
+        tl = {mode: [] for mode in modes}
+        for _ in range(iters):
+            for mode in modes:
+                tl[mode].append(timed(lambda: step(mode)))
+        for mode in modes:  # the peak of one step, the other modes' buffers released
+            conv.zero_grad(set_to_none=True)
+            xs.grad = vals.grad = None
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            step(mode)
+            torch.cuda.synchronize()
+            r[f"step_{mode}_peak_bytes"] = int(torch.cuda.max_memory_allocated())
+            r[f"step_{mode}_peak_over_resident_bytes"] = int(torch.cuda.max_memory_allocated()
+                                                             - base)
+    finally:
+        for v, x in saved.items():
+            if x is not None:
+                os.environ[v] = x
+    sl = {f"step_{mode}": summary(t) for mode, t in tl.items()}
+    r.update(sl)
+    r["ratio_attention_bwd_fused_to_rebuilt"] = round(
+        s["attention_bwd_fused"]["median_ms"] / s["attention_bwd_rebuilt"]["median_ms"], 4)
+    r["attention_bwd_fused_faster"] = bool(
+        1.0 - r["ratio_attention_bwd_fused_to_rebuilt"] > s["attention_bwd_rebuilt"]["spread"])
+    r["attention_bwd_fused_slower"] = bool(
+        r["ratio_attention_bwd_fused_to_rebuilt"] - 1.0 > s["attention_bwd_rebuilt"]["spread"])
+    for a, b in (("fused_fused", "fused_rebuilt"), ("fused_fused", "stored"),
+                 ("fused_rebuilt", "stored")):
+        r[f"ratio_step_{a}_to_{b}"] = round(
+            sl[f"step_{a}"]["median_ms"] / sl[f"step_{b}"]["median_ms"], 4)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--graphs", default="reddit:16,products:32")
@@ -409,6 +545,9 @@ def main():
             if "attention" in asked:
                 rs.append(run_attention(name, int(k), args.dim, H, args.iters, args.warmup,
                                         args.seed, dev))
+            if "attention_bwd" in asked:
+                rs.append(run_attention_bwd(name, int(k), args.dim, H, args.iters, args.warmup,
+                                            args.seed, dev))
             if "layer" in asked and H >= 2:
                 rs.append(run_layer(name, int(k), args.dim, H, args.iters, args.warmup,
                                     args.seed, dev))
