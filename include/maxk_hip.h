@@ -517,6 +517,76 @@ int maxk_gat_attention_heads_backward(
     size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Attention dropout: the GAT's dropout of the coefficients between the edge softmax and the
+ * aggregation, by a mask that is a pure function of (seed, head, edge) and is stored nowhere.
+ * The mask of head h and edge e (its CSR position, 0 <= e < num_e), for a rate p and a 64-bit
+ * seed:
+ *   (r0, r1, r2, r3) = Philox4x32-10(counter (e, 0, h >> 2, 0),
+ *                                    key (seed & 0xffffffff, seed >> 32))
+ *     -- multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, ten
+ *     rounds;
+ *   r = r[h & 3];  thr = min(floor(p * 2^32), 2^32 - 1), in double on the host;
+ *   the edge is dropped iff r < thr;  d_he = dropped ? 0 : scale,
+ *   scale = (float)(1 / (1 - (double)p)).
+ * Nothing else enters: not chunk_edges, not the work-item cut, not num_heads or the padded head
+ * count, not which entry evaluates it, so the three entries below and every call of them agree
+ * on the mask.  seed travels by value: a captured graph replays the same mask on every replay;
+ * a training loop that wants a fresh mask per step passes a fresh seed outside the capture.
+ * 0 <= p < 1 and not NaN, otherwise MAXK_ERR_INVALID naming p.  The reference has no counterpart.
+ *
+ * maxk_edge_dropout_heads: out[h,e] = w[h,e] * d_he, head-major f32 [num_heads, num_e]; out may
+ *   be w.  One elementwise kernel, no workspace.  It serves the stored path's forward (on
+ *   alpha), its backward (on grad_alpha) and the rebuilt backward of the fused path.  The stored
+ *   path therefore keeps two [num_heads, num_e] tensors for its backward, alpha for the softmax
+ *   backward and the dropped alpha for the aggregation: a known limit, the fused entries below
+ *   keep none.  Writes every element of out; num_e == 0 launches nothing.  A kept weight is the
+ *   correctly rounded w * scale, a dropped one w * 0 (a NaN or Inf stays NaN).
+ * maxk_gat_attention_heads_dropout: maxk_gat_attention_heads with
+ *   out[h, r, cbsr_idx[c,l]] += alpha[h,e] * d_he * cbsr_val[c,l].
+ *   row_max and row_sum are the statistics of the undropped softmax, bitwise those of
+ *   maxk_gat_attention_heads at the same chunk_edges: dropout follows the normalisation.  The
+ *   lane that computes an edge's weight evaluates its mask; the kernel sums p * (0 or 1) * value
+ *   and multiplies the row by scale after the division by z.
+ * maxk_gat_attention_heads_dropout_backward: maxk_gat_attention_heads_backward with
+ *   gz_he = alpha_he * (d_he * ga_he - t_hr) * (z_he > 0 ? 1 : negative_slope),
+ *   grad_cbsr[c,l] = sum_h sum_{e -> c} alpha_he * d_he * grad_out[h, r, cbsr_idx[c,l]],
+ *   t_hr as there, from the dropped out: sum_e alpha_he * d_he * ga_he is still the dot product
+ *   of out[h,r,:] and grad_out[h,r,:].  Same p and seed as the forward that produced out.
+ * Both take the arguments, shapes, workspace (the _workspace_size queries return the sizes of
+ *   the entries without dropout), memory contract, argument errors and repeatability of the
+ *   entries they extend; p == 0 runs those entries' kernels and is bitwise equal to them.
+ * Numerics (tests/attn_dropout_ref.py): the bounds of the entries without dropout carried
+ *   through the factor d <= scale, plus one rounding (u = 2^-24, relative) for the product by
+ *   scale.  Non-finite values follow the IEEE evaluation of the formulas with d as a factor:
+ *   0 * NaN and 0 * Inf are NaN, dropping does not shield.  For finite inputs a row all of whose
+ *   edges are dropped in head h has exact zeros in out[h, r, :].
+ * No global and no LDS atomics.
+ * ------------------------------------------------------------------------- */
+int maxk_edge_dropout_heads(const float *w, float *out, int32_t num_heads, int64_t num_e, float p,
+                            uint64_t seed, void *stream);
+size_t maxk_gat_attention_heads_dropout_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                       int64_t num_e, int32_t dim_origin,
+                                                       int32_t dim_k, int32_t num_heads,
+                                                       int32_t chunk_edges);
+int maxk_gat_attention_heads_dropout(
+    const int32_t *row_ptr, const int32_t *col_idx, const float *s_dst, const float *s_src,
+    float negative_slope, const float *cbsr_val, const uint8_t *cbsr_idx, float *out,
+    float *row_max, float *row_sum, int64_t num_rows, int64_t num_cols, int64_t num_e,
+    int32_t dim_origin, int32_t dim_k, int32_t num_heads, int32_t chunk_edges, float p,
+    uint64_t seed, void *workspace, size_t workspace_bytes, void *stream);
+size_t maxk_gat_attention_heads_dropout_backward_workspace_size(
+    int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+    int32_t num_heads, int32_t chunk_edges);
+int maxk_gat_attention_heads_dropout_backward(
+    const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
+    const int32_t *csc_eid, const float *s_dst, const float *s_src, float negative_slope,
+    const float *cbsr_val, const uint8_t *cbsr_idx, const float *out, const float *row_max,
+    const float *row_sum, const float *grad_out, float *grad_s_dst, float *grad_s_src,
+    float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+    int32_t dim_k, int32_t num_heads, int32_t chunk_edges, float p, uint64_t seed,
+    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Backward outer-product sampled SpMM (SSpMM):
  *   grad_cbsr[c,l] = sum_{e=(r->c)} edge_val[e] * grad_out[r, cbsr_idx[c,l]] / row_div[r]
  *                  = (A^T diag(1/row_div) G)[c, cbsr_idx[c,l]]     (from the CSR of A)

@@ -38,8 +38,12 @@
 // the result is bitwise repeatable, and head h's slice is computed from head h's scores only.
 // LDS per wave as the multi-head forward (G * DS floats); 87 to 96 VGPRs at HP = 2 and 4 (five
 // waves per SIMD), 108 or 109 at HP = 8 (four); no scratch.
+// maxk_gat_attention_heads_dropout is the same walk with the attention-dropout mask of
+// attn_dropout.h multiplied in (the DROP instantiations): out sums alpha * d * value, the
+// statistics stay those of the undropped softmax, p == 0 launches the kernels without a mask.
 #include <cmath>
 
+#include "attn_dropout.h"
 #include "cbsr_pack.h"
 #include "edge_softmax.h"
 
@@ -109,18 +113,36 @@ struct WeightLane {
 // head's score ss[c * HP + head]; returns the lane's sum of p (the same in every lane of a
 // group).  active: the group has an edge slot and a head in this pass; else it writes its trash
 // column only.  POISON: p = NaN and nothing is summed (the rows whose z is no positive number).
-template <int KG, int HP, int U, bool POISON>
+// DROP (attn_dropout.h): a wave step holds EP * U edges and the pass's heads lie in dp.qp <= 2
+// quads, so one Philox evaluation per lane -- lane t on the edge at offset t % span of the next
+// S = 64 / (EP * U * qp) steps (span = S * EP * U; its CSR position is sb + its index in the
+// piece) and the quad dp.q0 + t / span -- serves S steps: four ballots, one per head of a quad,
+// carry the bits, and each group keeps its head's 64 (`mine`).  The sum of p takes the unmasked
+// weights and the products p * (0 or 1): a dropped NaN or Inf stays NaN.
+struct DropPass {
+    int q0, qp, head;  // the pass's first quad of heads and their number; the group's head
+};
+template <int KG, int HP, int U, bool POISON, bool DROP>
 __device__ __forceinline__ float walk_attn(float *acc_g, const int32_t *__restrict__ col_idx,
                                            const float *__restrict__ ss, const WeightLane &wl,
                                            float slope, const uint8_t *__restrict__ rec, int RS,
                                            int sb, int se, int k, int trash, int EP, int eg,
-                                           bool active, int lane) {
+                                           bool active, int lane, const MaskArg<DROP> &dm,
+                                           const DropPass &dp) {
     constexpr int G = kWave / KG;
     const int l0 = lane % KG, grp = lane / KG;
     const int n = se - sb;  // wave-uniform, <= 2 * chunk
     const auto crs = wave_buffer(col_idx + sb, (uint32_t)n * 4u);
     const auto rrs = wave_buffer(rec, 0xffffffffu);  // offsets < num_cols * RS < 2^32
     float ps = 0.f;
+    const int EU = EP * U;
+    int S = 1, span_log = 0, js = 0, qsel = 0;
+    uint64_t mine = 0;
+    if constexpr (DROP) {
+        S = kWave / (EU * dp.qp);  // powers of two, EU * qp <= 64
+        span_log = 31 - __clz(S * EU);
+        qsel = min(max((dp.head >> 2) - dp.q0, 0), dp.qp - 1);
+    }
     for (int base = 0; base < n; base += EP * U) {
         int c[U];
         float w[U];
@@ -139,11 +161,24 @@ __device__ __forceinline__ float walk_attn(float *acc_g, const int32_t *__restri
             const int ct = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, it * 4, 0, 0);
             const float x = ss[(uint32_t)ct * (uint32_t)HP + (uint32_t)wl.head];
             const float pt = wl.on && it < n ? expf(leaky(wl.sdh + x, slope) - wl.shift) : 0.f;
+            if constexpr (DROP) {
+                if (js == 0) {  // wave-uniform: the masks of this and the next S - 1 steps
+                    const uint32_t bits =
+                        drop_bits(dm, (uint32_t)(sb + base + (lane & ((1 << span_log) - 1))),
+                                  (uint32_t)(dp.q0 + (lane >> span_log)));
+                    const uint64_t b0 = __ballot(bits & 1u), b1 = __ballot(bits & 2u),
+                                   b2 = __ballot(bits & 4u), b3 = __ballot(bits & 8u);
+                    const int hb = dp.head & 3;
+                    mine = (hb == 0 ? b0 : hb == 1 ? b1 : hb == 2 ? b2 : b3) >> (qsel << span_log);
+                }
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 w[u] = __shfl(pt, u * G + grp);
                 ps += w[u];
+                if constexpr (DROP) w[u] *= (mine >> (js * EU + u * EP + eg)) & 1 ? 0.f : 1.f;
             }
+            if constexpr (DROP) js = js + 1 == S ? 0 : js + 1;
         }
         for (int lb = 0; lb < k; lb += KG) {  // one pass unless k > 64
             const int l = lb + l0;
@@ -166,10 +201,11 @@ __device__ __forceinline__ float walk_attn(float *acc_g, const int32_t *__restri
 }
 
 // dst[0:D] = (acc[0:D] + acc[stride + 0:D] + ... over nc copies) / div; the copies read are
-// zeroed.  One wave.
+// zeroed.  One wave.  DROP: the quotient times mul, the mask's scale.
+template <bool DROP>
 __device__ __forceinline__ void flush_head(float *acc, int nc, int stride, float *__restrict__ dst,
                                            int D, float div, bool scale, bool vec, bool nt,
-                                           int lane) {
+                                           int lane, float mul) {
     if (vec) {
         for (int j = lane * 4; j < D; j += kWave * 4) {
             float4 a = *reinterpret_cast<float4 *>(&acc[j]);
@@ -188,6 +224,12 @@ __device__ __forceinline__ void flush_head(float *acc, int nc, int stride, float
                 a.y = a.y / div;
                 a.z = a.z / div;
                 a.w = a.w / div;
+                if constexpr (DROP) {
+                    a.x *= mul;
+                    a.y *= mul;
+                    a.z *= mul;
+                    a.w *= mul;
+                }
             }
             if (nt)  // output rows streamed past the caches (the record lines stay)
                 __builtin_nontemporal_store(__builtin_bit_cast(f32x4, a),
@@ -203,14 +245,18 @@ __device__ __forceinline__ void flush_head(float *acc, int nc, int stride, float
                 a += acc[g * stride + j];
                 acc[g * stride + j] = 0.f;
             }
-            dst[j] = scale ? a / div : a;
+            if (scale) a = DROP ? a / div * mul : a / div;
+            dst[j] = a;
         }
     }
 }
 
 // Five waves per SIMD where the registers allow it without scratch (HP = 2, 4: at most 96
-// VGPRs); HP = 8 takes 108 or 109 and runs four.
-template <int KG, int HP, int U>
+// VGPRs); HP = 8 takes 108 or 109 and runs four.  DROP keeps the same waves: at HP = 2 and 4 the
+// Philox rounds then spill 12 to 60 bytes per lane around the once-in-S-steps evaluation, which
+// measured faster than four waves without scratch (the forward's cost of the mask 1.09 to 1.13
+// against 1.23 to 1.30 Reddit-sized; profiles/r17/attn_dropout/); HP = 8 takes 124 or 125.
+template <int KG, int HP, int U, bool DROP>
 __global__ __launch_bounds__(kBlock, HP == 8 ? 4 : 5) void gath_fwd_kernel(
     const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
     const VecF<HP> *__restrict__ ss_t, const float *__restrict__ s_dst, float slope,
@@ -218,7 +264,7 @@ __global__ __launch_bounds__(kBlock, HP == 8 ? 4 : 5) void gath_fwd_kernel(
     float *__restrict__ row_max, float *__restrict__ row_sum, float *__restrict__ slab,
     float *__restrict__ slab_m, float *__restrict__ slab_z, int32_t *__restrict__ slab_row,
     int num_rows, int64_t num_e, int D, int DS, int k, int chunk, int n_items, int H, int HC,
-    int flags) {
+    int flags, MaskArg<DROP> dm) {
     // flags: bit 0 16-B row stores (D % 4 == 0, out 16-B aligned), bit 1 non-temporal out rows
     constexpr int G = kWave / KG;  // lane groups = LDS copies per wave
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -274,8 +320,10 @@ __global__ __launch_bounds__(kBlock, HP == 8 ? 4 : 5) void gath_fwd_kernel(
             float ps = 0.f;
             wave_lds_fence();
             if (n > 0)
-                ps = walk_attn<KG, HP, U, false>(acc_g, col_idx, ss, wl, slope, rec, RS, (int)sb,
-                                                 (int)se, k, DS - 1, EP, eg, active, lane);
+                ps = walk_attn<KG, HP, U, false, DROP>(
+                    acc_g, col_idx, ss, wl, slope, rec, RS, (int)sb, (int)se, k, DS - 1, EP, eg,
+                    active, lane, dm,
+                    DropPass{h0 >> 2, ((min(h0 + HC, H) - 1) >> 2) - (h0 >> 2) + 1, head});
             // z of head h0 + j: its EP groups' sums in group order
             auto z_of = [&](int j) {
                 float z = 0.f;
@@ -287,16 +335,19 @@ __global__ __launch_bounds__(kBlock, HP == 8 ? 4 : 5) void gath_fwd_kernel(
                 if (!(z_of(j) > 0.f)) bad |= 1 << j;
             if (whole && n > 0 && bad) {  // rare: NaN wherever such a head's row has an addend
                 wave_lds_fence();
-                walk_attn<KG, HP, U, true>(acc_g, col_idx, ss, wl, slope, rec, RS, (int)sb,
-                                           (int)se, k, DS - 1, EP, eg,
-                                           active && ((bad >> hh) & 1), lane);
+                walk_attn<KG, HP, U, true, false>(acc_g, col_idx, ss, wl, slope, rec, RS, (int)sb,
+                                                  (int)se, k, DS - 1, EP, eg,
+                                                  active && ((bad >> hh) & 1), lane, NoMask{},
+                                                  DropPass{0, 1, 0});
             }
             wave_lds_fence();
             for (int j = 0; j < HC && h0 + j < H; ++j) {
                 const float zj = z_of(j);
                 const bool ok = !((bad >> j) & 1);
-                flush_head(acc + j * DS, EP, HC * DS, dst + (int64_t)(h0 + j) * hstride, D, zj,
-                           whole && ok, vec, nt && to_out, lane);
+                float mul = 1.f;
+                if constexpr (DROP) mul = dm.scale;
+                flush_head<DROP>(acc + j * DS, EP, HC * DS, dst + (int64_t)(h0 + j) * hstride, D,
+                                 zj, whole && ok, vec, nt && to_out, lane, mul);
                 // the head's maximum sits in the lanes of group j (edge slot 0, head h0 + j)
                 const float mj = uniform(__shfl(mh, j * KG));
                 if (lane == 0) {
@@ -339,14 +390,15 @@ __global__ __launch_bounds__(kBlock, HP == 8 ? 4 : 5) void gath_fwd_kernel(
 // The merge of a hub row's pieces, one head per blockIdx.y, 16 lanes per item as
 // slab_fixup_kernel: the thread group of the first item holding a slab of the row merges the
 // owner's piece (in out and the statistics) and the row's slabs in item order.  Every hub row
-// has a slab: it is longer than an item.
+// has a slab: it is longer than an item.  DROP: the merged quotient times mul, the mask's scale.
+template <bool DROP>
 __global__ __launch_bounds__(kBlock) void gath_fixup_kernel(
     const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
     const uint8_t *__restrict__ rec, int RS, int k, const float *__restrict__ slab_all,
     const float *__restrict__ slab_m_all, const float *__restrict__ slab_z_all,
     const int32_t *__restrict__ slab_row, float *__restrict__ out_all,
     float *__restrict__ row_max_all, float *__restrict__ row_sum_all, int64_t num_rows, int D,
-    int n_items) {
+    int n_items, float mul) {
     const int item = (int)((blockIdx.x * (int64_t)kBlock + threadIdx.x) / 16);
     const int g = threadIdx.x % 16;
     if (item >= n_items) return;
@@ -373,7 +425,7 @@ __global__ __launch_bounds__(kBlock) void gath_fixup_kernel(
         for (int j = g; j < D; j += 16) {
             float a = o[j] * c0;
             for (int i = 0; i < n; ++i) a += sl[(int64_t)i * D + j] * expf(sm[i] - shift);
-            o[j] = a / z;
+            o[j] = DROP ? a / z * mul : a / z;
         }
     } else {  // rare: NaN wherever the row has an addend, 0 elsewhere
         for (int j = g; j < D; j += 16) o[j] = 0.f;
@@ -486,12 +538,13 @@ int launch_interleave(const float *s_src, void *ss_t, int H, int64_t num_cols, h
     return MAXK_OK;
 }
 
-template <int HP>
+template <int HP, bool DROP>
 int launch_attention(const int32_t *row_ptr, const int32_t *col_idx, const float *s_dst,
                      const float *s_src, float slope, const float *cbsr_val,
                      const uint8_t *cbsr_idx, float *out, float *row_max, float *row_sum,
                      int64_t num_rows, int64_t num_cols, int64_t num_e, int D, int k, int H,
-                     const AttnLayout &L, void *workspace, hipStream_t s) {
+                     const AttnLayout &L, void *workspace, hipStream_t s,
+                     const MaskArg<DROP> &dm) {
     char *ws = reinterpret_cast<char *>(workspace);
     uint8_t *rec = reinterpret_cast<uint8_t *>(ws);
     VecF<HP> *ss_t = reinterpret_cast<VecF<HP> *>(ws + L.ss_off);
@@ -511,17 +564,19 @@ int launch_attention(const int32_t *row_ptr, const int32_t *col_idx, const float
                       ((MAXK_FWD_OUT_NT == 1 || (MAXK_FWD_OUT_NT == 2 && big)) ? 2 : 0);
     const bool ok = with_const<8, 16, 32, 64>(L.kg, [&](auto kg_c) {
         constexpr int KG = decltype(kg_c)::value;
-        hipLaunchKernelGGL((gath_fwd_kernel<KG, HP, U>), grid, dim3(kBlock), lds, s, row_ptr,
+        hipLaunchKernelGGL((gath_fwd_kernel<KG, HP, U, DROP>), grid, dim3(kBlock), lds, s, row_ptr,
                            col_idx, ss_t, s_dst, slope, rec, L.RS, out, row_max, row_sum, slab,
                            slab_m, slab_z, slab_row, (int)num_rows, num_e, D, L.DS, k, L.chunk,
-                           L.n_items, H, L.hc, flags);
+                           L.n_items, H, L.hc, flags, dm);
     });
     if (!ok) return bad_lanes(L.kg);
     MAXK_LAUNCHED("gath_fwd_kernel");
-    hipLaunchKernelGGL(gath_fixup_kernel,
+    float mul = 1.f;
+    if constexpr (DROP) mul = dm.scale;
+    hipLaunchKernelGGL(gath_fixup_kernel<DROP>,
                        dim3((unsigned)ceil_div(L.n_items, kBlock / 16), (unsigned)H), dim3(kBlock),
                        0, s, row_ptr, col_idx, rec, L.RS, k, slab, slab_m, slab_z, slab_row, out,
-                       row_max, row_sum, num_rows, D, L.n_items);
+                       row_max, row_sum, num_rows, D, L.n_items, mul);
     MAXK_LAUNCHED("gath_fixup_kernel");
     return MAXK_OK;
 }
@@ -555,15 +610,14 @@ extern "C" size_t maxk_gat_attention_heads_workspace_size(int64_t num_rows, int6
     return attn_layout(num_rows, num_cols, num_e, dim_origin, dim_k, num_heads, chunk_edges).total;
 }
 
-extern "C" int maxk_gat_attention_heads(const int32_t *row_ptr, const int32_t *col_idx,
-                                        const float *s_dst, const float *s_src,
-                                        float negative_slope, const float *cbsr_val,
-                                        const uint8_t *cbsr_idx, float *out, float *row_max,
-                                        float *row_sum, int64_t num_rows, int64_t num_cols,
-                                        int64_t num_e, int32_t dim_origin, int32_t dim_k,
-                                        int32_t num_heads, int32_t chunk_edges, void *workspace,
-                                        size_t workspace_bytes, void *stream) {
-    clear_error();
+namespace {
+// Both attention entries; dm: the dropout entry's mask, null for none.
+int attention_heads(const int32_t *row_ptr, const int32_t *col_idx, const float *s_dst,
+                    const float *s_src, float negative_slope, const float *cbsr_val,
+                    const uint8_t *cbsr_idx, float *out, float *row_max, float *row_sum,
+                    int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+                    int32_t dim_k, int32_t num_heads, int32_t chunk_edges, void *workspace,
+                    size_t workspace_bytes, void *stream, const DropMask *dm) {
     if (int rc = check_heads(num_heads)) return rc;
     if (int rc = check_sizes(num_rows, num_cols, num_e, chunk_edges)) return rc;
     if (int rc = check_slope(negative_slope)) return rc;
@@ -593,15 +647,61 @@ extern "C" int maxk_gat_attention_heads(const int32_t *row_ptr, const int32_t *c
                      ((uintptr_t)s_src & 3) == 0 && ((uintptr_t)out & 3) == 0 &&
                      ((uintptr_t)row_max & 3) == 0 && ((uintptr_t)row_sum & 3) == 0,
                  "float buffers must be 4-B aligned");
-#define MAXK_GATH_FWD(HP)                                                                        \
-    launch_attention<HP>(row_ptr, col_idx, s_dst, s_src, negative_slope, cbsr_val, cbsr_idx, out, \
-                         row_max, row_sum, num_rows, num_cols, num_e, D, k, H, L, workspace, s)
+#define MAXK_GATH_FWD(HP, DROP, DM)                                                             \
+    launch_attention<HP, DROP>(row_ptr, col_idx, s_dst, s_src, negative_slope, cbsr_val,        \
+                               cbsr_idx, out, row_max, row_sum, num_rows, num_cols, num_e, D, k, \
+                               H, L, workspace, s, DM)
+    if (dm) {
+        switch (L.hp) {
+            case 2: return MAXK_GATH_FWD(2, true, *dm);
+            case 4: return MAXK_GATH_FWD(4, true, *dm);
+            default: return MAXK_GATH_FWD(8, true, *dm);
+        }
+    }
     switch (L.hp) {
-        case 2: return MAXK_GATH_FWD(2);
-        case 4: return MAXK_GATH_FWD(4);
-        default: return MAXK_GATH_FWD(8);
+        case 2: return MAXK_GATH_FWD(2, false, NoMask{});
+        case 4: return MAXK_GATH_FWD(4, false, NoMask{});
+        default: return MAXK_GATH_FWD(8, false, NoMask{});
     }
 #undef MAXK_GATH_FWD
+}
+}  // namespace
+
+extern "C" int maxk_gat_attention_heads(const int32_t *row_ptr, const int32_t *col_idx,
+                                        const float *s_dst, const float *s_src,
+                                        float negative_slope, const float *cbsr_val,
+                                        const uint8_t *cbsr_idx, float *out, float *row_max,
+                                        float *row_sum, int64_t num_rows, int64_t num_cols,
+                                        int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                                        int32_t num_heads, int32_t chunk_edges, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+    clear_error();
+    return attention_heads(row_ptr, col_idx, s_dst, s_src, negative_slope, cbsr_val, cbsr_idx, out,
+                           row_max, row_sum, num_rows, num_cols, num_e, dim_origin, dim_k,
+                           num_heads, chunk_edges, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" size_t maxk_gat_attention_heads_dropout_workspace_size(
+    int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+    int32_t num_heads, int32_t chunk_edges) {
+    return maxk_gat_attention_heads_workspace_size(num_rows, num_cols, num_e, dim_origin, dim_k,
+                                                   num_heads, chunk_edges);
+}
+
+extern "C" int maxk_gat_attention_heads_dropout(
+    const int32_t *row_ptr, const int32_t *col_idx, const float *s_dst, const float *s_src,
+    float negative_slope, const float *cbsr_val, const uint8_t *cbsr_idx, float *out,
+    float *row_max, float *row_sum, int64_t num_rows, int64_t num_cols, int64_t num_e,
+    int32_t dim_origin, int32_t dim_k, int32_t num_heads, int32_t chunk_edges, float p,
+    uint64_t seed, void *workspace, size_t workspace_bytes, void *stream) {
+    clear_error();
+    if (int rc = check_dropout(p)) return rc;
+    // p == 0 drops nothing and scales by 1: the kernels of the entry without dropout
+    const DropMask dm = drop_mask(p, seed);
+    return attention_heads(row_ptr, col_idx, s_dst, s_src, negative_slope, cbsr_val, cbsr_idx, out,
+                           row_max, row_sum, num_rows, num_cols, num_e, dim_origin, dim_k,
+                           num_heads, chunk_edges, workspace, workspace_bytes, stream,
+                           p > 0.f ? &dm : nullptr);
 }
 
 extern "C" size_t maxk_gat_edge_alpha_heads_workspace_size(int32_t num_heads, int64_t num_rows,

@@ -42,8 +42,13 @@
 //  4. csc_sum_rows: grad_cbsr from T through the CSC, in slot order (the csc phase 2).
 // No global atomics, no LDS atomics; every sum has an order fixed by (graph, chunk, k, H).  Head
 // h's score gradients are computed from head h's scores, statistics, out and grad_out alone.
+// maxk_gat_attention_heads_dropout_backward is the same walk under the attention-dropout mask of
+// attn_dropout.h (the DROP instantiations): gz = alpha * (d * ga - t) * (z > 0 ? 1 : slope) and
+// T gains alpha * d * x; t is still out . grad_out, out being the dropped forward's, since
+// sum_e alpha_e d_e ga_e is that dot product.  p == 0 launches the kernels without a mask.
 #include <cmath>
 
+#include "attn_dropout.h"
 #include "cbsr_pack.h"
 #include "edge_softmax.h"
 #include "sspmm_bwd.h"
@@ -90,15 +95,19 @@ struct HeadLane {
 
 // The edges [sb, se) (sb < se) of one row whose grad_out rows are staged in grow: stores their
 // T rows and gzT vectors; returns this lane's sum of the gz of head lane % KG over its group's
-// edges (lanes % KG >= H: 0).
-template <int KG, int HP, int U>
+// edges (lanes % KG >= H: 0).  DROP (attn_dropout.h): lane j < U * QP of a group evaluates the
+// mask of the group's edge j % U for the quad of heads j / U, QP = ceil(HP / 4) quads; lane h
+// fetches its head's bit with one shuffle per edge and keeps d = 0 or scale beside alpha:
+// T gains alpha * d * x and gz = alpha * (d * ga - t), t from the dropped out.
+template <int KG, int HP, int U, bool DROP>
 __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
                                                 const int32_t *__restrict__ col_idx,
                                                 const float *__restrict__ ss,
                                                 const uint8_t *__restrict__ rec, int RS,
                                                 float *__restrict__ T, float *__restrict__ gzT,
                                                 int H, int D, int sb, int se, int k,
-                                                const HeadLane &hd, float slope, int lane) {
+                                                const HeadLane &hd, float slope, int lane,
+                                                const MaskArg<DROP> &dm) {
     constexpr int G = kWave / KG;
     const int grp = lane / KG, l0 = lane % KG;
     const int lane0 = lane - l0;  // the group's first lane
@@ -132,6 +141,32 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
                 pos |= (z > 0.f ? 1u : 0u) << u;
             }
         }
+        uint32_t gone = 0u;  // DROP, lane h: bit u, head h of the group's edge u is dropped
+        if constexpr (DROP) {
+            constexpr int QP = (HP + 3) / 4;
+            static_assert(U * QP <= KG, "a group evaluates its step's masks in one round");
+            const uint32_t bits = drop_bits(
+                dm, (uint32_t)(sb + base + (l0 % U) * G + grp), (uint32_t)((l0 / U) % QP));
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t b = __shfl(bits, lane0 + ((l0 >> 2) % QP) * U + u);
+                gone |= ((b >> (l0 & 3)) & 1u) << u;
+            }
+        }
+        auto dk = [&](int u) {  // the mask factor d
+            if constexpr (DROP) return (gone >> u) & 1u ? 0.f : dm.scale;
+            else return 1.f;
+        };
+        // the coefficient of the feature gradient: alpha, under DROP alpha * d
+        float ad[DROP ? U : 1];
+        if constexpr (DROP) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) ad[u] = al[u] * dk(u);
+        }
+        auto coef = [&](int u) {
+            if constexpr (DROP) return ad[u];
+            else return al[u];
+        };
         float ga[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) ga[u] = 0.f;
@@ -158,7 +193,7 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const float x = gh[s[u]];
-                        const float a = __shfl(al[u], lane0 + h);
+                        const float a = __shfl(coef(u), lane0 + h);
                         // a slot without a kept value adds nothing, whatever x is
                         const float d = lane_tree<KG, Sum>((keep >> u) & 1u ? v[u] * x : 0.f);
                         ga[u] = l0 == h ? d : ga[u];
@@ -224,7 +259,7 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
 #pragma unroll
                         for (int u = 0; u < U; ++u) {
                             const float x = gh[s[u]];
-                            const float a = __shfl(al[u], lane0 + h);
+                            const float a = __shfl(coef(u), lane0 + h);
                             tc[u] = h == 0 ? a * x : __builtin_fmaf(a, x, tc[u]);
                         }
                     }
@@ -241,7 +276,9 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = base + u * G + grp;
-            float gz = al[u] * (ga[u] - hd.t);
+            float gz;
+            if constexpr (DROP) gz = al[u] * (dk(u) * ga[u] - hd.t);
+            else gz = al[u] * (ga[u] - hd.t);
             gz *= (pos >> u) & 1u ? 1.f : slope;
             gsum += hon && i < n ? gz : 0.f;
             __builtin_amdgcn_raw_buffer_store_b32(
@@ -251,15 +288,16 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
     return gsum;
 }
 
-template <int KG, int HP, int U>
-__global__ __launch_bounds__(kBlock) void gath_bwd_kernel(
+// DROP: held to the four waves per SIMD of the kernels without a mask.
+template <int KG, int HP, int U, bool DROP>
+__global__ __launch_bounds__(kBlock, DROP ? 4 : 1) void gath_bwd_kernel(
     const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
     const float *__restrict__ ss, const float *__restrict__ s_dst, float slope,
     const uint8_t *__restrict__ rec, int RS, const float *__restrict__ out,
     const float *__restrict__ row_max, const float *__restrict__ row_sum,
     const float *__restrict__ grad_out, float *__restrict__ T, float *__restrict__ gzT,
     float *__restrict__ grad_s_dst, SlotsH sl, int num_rows, int64_t num_e, int D, int DS, int k,
-    int chunk, int n_items, int H, int vec) {
+    int chunk, int n_items, int H, int vec, MaskArg<DROP> dm) {
     constexpr int G = kWave / KG;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int wid = threadIdx.x / kWave;
@@ -301,9 +339,9 @@ __global__ __launch_bounds__(kBlock) void gath_bwd_kernel(
                 hd.t = l0 == h ? th : hd.t;
             }
             wave_lds_fence();
-            const float gsum = walk_piece_bwd<KG, HP, U>(grow, DS, col_idx, ss, rec, RS, T, gzT,
-                                                         H, D, (int)p.sb, (int)p.se, k, hd, slope,
-                                                         lane);
+            const float gsum = walk_piece_bwd<KG, HP, U, DROP>(grow, DS, col_idx, ss, rec, RS, T,
+                                                               gzT, H, D, (int)p.sb, (int)p.se, k,
+                                                               hd, slope, lane, dm);
             float tot = 0.f;  // head l0's sum over the piece: the groups in group order
 #pragma unroll
             for (int g = 0; g < G; ++g) tot += __shfl(gsum, g * KG + l0);
@@ -382,7 +420,7 @@ BwdLayout bwd_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, i
     return L;
 }
 
-template <int HP>
+template <int HP, bool DROP>
 int launch_attention_bwd(const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
                          const int32_t *csc_eid, const float *s_dst, const float *s_src,
                          float slope, const float *cbsr_val, const uint8_t *cbsr_idx,
@@ -390,7 +428,7 @@ int launch_attention_bwd(const int32_t *row_ptr, const int32_t *col_idx, const i
                          const float *grad_out, float *grad_s_dst, float *grad_s_src,
                          float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e,
                          int D, int k, int H, int chunk_edges, const BwdLayout &L, void *workspace,
-                         hipStream_t s) {
+                         hipStream_t s, const MaskArg<DROP> &dm) {
     char *ws = reinterpret_cast<char *>(workspace);
     float *T = reinterpret_cast<float *>(ws);
     uint8_t *rec = reinterpret_cast<uint8_t *>(ws + L.rec_off);
@@ -408,11 +446,11 @@ int launch_attention_bwd(const int32_t *row_ptr, const int32_t *col_idx, const i
     const int vec = D % 4 == 0 && ((uintptr_t)grad_out & 15) == 0 && ((uintptr_t)out & 15) == 0;
     const bool ok = with_const<8, 16, 32, 64>(L.kg, [&](auto kg_c) {
         constexpr int KG = decltype(kg_c)::value;
-        hipLaunchKernelGGL((gath_bwd_kernel<KG, HP, U>), item_grid(L.n_items), dim3(kBlock), lds,
+        hipLaunchKernelGGL((gath_bwd_kernel<KG, HP, U, DROP>), item_grid(L.n_items), dim3(kBlock), lds,
                            s, row_ptr, col_idx, reinterpret_cast<const float *>(ss_t), s_dst,
                            slope, rec, L.RS, out, row_max, row_sum, grad_out, T,
                            reinterpret_cast<float *>(gzT), grad_s_dst, sl, (int)num_rows, num_e,
-                           D, L.DS, k, L.chunk, L.n_items, H, vec);
+                           D, L.DS, k, L.chunk, L.n_items, H, vec, dm);
     });
     if (!ok) return bad_lanes(L.kg);
     MAXK_LAUNCHED("gath_bwd_kernel");
@@ -439,15 +477,16 @@ extern "C" size_t maxk_gat_attention_heads_backward_workspace_size(
     return bwd_layout(num_rows, num_cols, num_e, dim_origin, dim_k, num_heads, chunk_edges).total;
 }
 
-extern "C" int maxk_gat_attention_heads_backward(
+namespace {
+// Both backward entries; dm: the dropout entry's mask, null for none.
+int attention_heads_backward(
     const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
     const int32_t *csc_eid, const float *s_dst, const float *s_src, float negative_slope,
     const float *cbsr_val, const uint8_t *cbsr_idx, const float *out, const float *row_max,
     const float *row_sum, const float *grad_out, float *grad_s_dst, float *grad_s_src,
     float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
     int32_t dim_k, int32_t num_heads, int32_t chunk_edges, void *workspace,
-    size_t workspace_bytes, void *stream) {
-    clear_error();
+    size_t workspace_bytes, void *stream, const DropMask *dm) {
     if (int rc = check_heads(num_heads)) return rc;
     if (int rc = check_sizes(num_rows, num_cols, num_e, chunk_edges)) return rc;
     if (int rc = check_slope(negative_slope)) return rc;
@@ -484,15 +523,66 @@ extern "C" int maxk_gat_attention_heads_backward(
                      ((uintptr_t)grad_out & 3) == 0 && ((uintptr_t)grad_s_dst & 3) == 0 &&
                      ((uintptr_t)grad_s_src & 3) == 0 && ((uintptr_t)grad_cbsr & 3) == 0,
                  "float buffers must be 4-B aligned");
-#define MAXK_GATH_BWD(HP)                                                                       \
-    launch_attention_bwd<HP>(row_ptr, col_idx, col_ptr, csc_eid, s_dst, s_src, negative_slope,  \
-                             cbsr_val, cbsr_idx, out, row_max, row_sum, grad_out, grad_s_dst,   \
-                             grad_s_src, grad_cbsr, num_rows, num_cols, num_e, D, k, H,         \
-                             chunk_edges, L, workspace, s)
+#define MAXK_GATH_BWD(HP, DROP, DM)                                                             \
+    launch_attention_bwd<HP, DROP>(row_ptr, col_idx, col_ptr, csc_eid, s_dst, s_src,            \
+                                   negative_slope, cbsr_val, cbsr_idx, out, row_max, row_sum,   \
+                                   grad_out, grad_s_dst, grad_s_src, grad_cbsr, num_rows,       \
+                                   num_cols, num_e, D, k, H, chunk_edges, L, workspace, s, DM)
+    if (dm) {
+        switch (L.hp) {
+            case 2: return MAXK_GATH_BWD(2, true, *dm);
+            case 4: return MAXK_GATH_BWD(4, true, *dm);
+            default: return MAXK_GATH_BWD(8, true, *dm);
+        }
+    }
     switch (L.hp) {
-        case 2: return MAXK_GATH_BWD(2);
-        case 4: return MAXK_GATH_BWD(4);
-        default: return MAXK_GATH_BWD(8);
+        case 2: return MAXK_GATH_BWD(2, false, NoMask{});
+        case 4: return MAXK_GATH_BWD(4, false, NoMask{});
+        default: return MAXK_GATH_BWD(8, false, NoMask{});
     }
 #undef MAXK_GATH_BWD
+}
+}  // namespace
+
+extern "C" int maxk_gat_attention_heads_backward(
+    const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
+    const int32_t *csc_eid, const float *s_dst, const float *s_src, float negative_slope,
+    const float *cbsr_val, const uint8_t *cbsr_idx, const float *out, const float *row_max,
+    const float *row_sum, const float *grad_out, float *grad_s_dst, float *grad_s_src,
+    float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+    int32_t dim_k, int32_t num_heads, int32_t chunk_edges, void *workspace,
+    size_t workspace_bytes, void *stream) {
+    clear_error();
+    return attention_heads_backward(row_ptr, col_idx, col_ptr, csc_eid, s_dst, s_src, negative_slope,
+                                    cbsr_val, cbsr_idx, out, row_max, row_sum, grad_out,
+                                    grad_s_dst, grad_s_src, grad_cbsr, num_rows, num_cols, num_e,
+                                    dim_origin, dim_k, num_heads, chunk_edges, workspace,
+                                    workspace_bytes, stream, nullptr);
+}
+
+extern "C" size_t maxk_gat_attention_heads_dropout_backward_workspace_size(
+    int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+    int32_t num_heads, int32_t chunk_edges) {
+    return maxk_gat_attention_heads_backward_workspace_size(num_rows, num_cols, num_e, dim_origin,
+                                                            dim_k, num_heads, chunk_edges);
+}
+
+extern "C" int maxk_gat_attention_heads_dropout_backward(
+    const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
+    const int32_t *csc_eid, const float *s_dst, const float *s_src, float negative_slope,
+    const float *cbsr_val, const uint8_t *cbsr_idx, const float *out, const float *row_max,
+    const float *row_sum, const float *grad_out, float *grad_s_dst, float *grad_s_src,
+    float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+    int32_t dim_k, int32_t num_heads, int32_t chunk_edges, float p, uint64_t seed,
+    void *workspace, size_t workspace_bytes, void *stream) {
+    clear_error();
+    if (int rc = check_dropout(p)) return rc;
+    // p == 0 drops nothing and scales by 1: the kernels of the entry without dropout
+    const DropMask dm = drop_mask(p, seed);
+    return attention_heads_backward(row_ptr, col_idx, col_ptr, csc_eid, s_dst, s_src, negative_slope,
+                                    cbsr_val, cbsr_idx, out, row_max, row_sum, grad_out,
+                                    grad_s_dst, grad_s_src, grad_cbsr, num_rows, num_cols, num_e,
+                                    dim_origin, dim_k, num_heads, chunk_edges, workspace,
+                                    workspace_bytes, stream,
+                                    p > 0.f ? &dm : nullptr);
 }

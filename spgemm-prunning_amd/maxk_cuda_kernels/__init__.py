@@ -51,7 +51,7 @@ __all__ = [
     "sspmm_backward_heads", "heads_backward_route",
     "gat_edge_softmax_heads", "gat_edge_softmax_heads_backward", "heads_softmax_route",
     "gat_attention_heads", "gat_edge_alpha_heads", "heads_attention_route",
-    "gat_attention_heads_backward", "heads_attention_backward_route",
+    "gat_attention_heads_backward", "heads_attention_backward_route", "edge_dropout_heads",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -667,13 +667,17 @@ def heads_softmax_route(num_heads: int, num_rows: int, num_e: int) -> str:
 def gat_attention_heads(indptr: torch.Tensor, indices: torch.Tensor, s_dst: torch.Tensor,
                         s_src: torch.Tensor, cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor,
                         dim_origin: int, negative_slope: float = 0.2, chunk: int = 0,
-                        out: Optional[torch.Tensor] = None, validate: Optional[bool] = None):
+                        out: Optional[torch.Tensor] = None, validate: Optional[bool] = None,
+                        dropout: float = 0.0, seed: int = 0):
     """(out [H, num_rows, D], row_max [H, num_rows], row_sum [H, num_rows]): the attention
     aggregation of H GAT heads in one walk of the graph (maxk_gat_attention_heads) -- what
     gat_edge_softmax_heads followed by spgemm_forward_heads compute, without the coefficients
     [H, E] ever being stored.  row_max and row_sum are the softmax statistics of every row and
     head (the largest logit and the sum of exp(logit - max)); gat_edge_alpha_heads rebuilds the
-    coefficients from them.  1 <= H <= MAX_HEADS; bitwise repeatable."""
+    coefficients from them.  1 <= H <= MAX_HEADS; bitwise repeatable.
+    dropout > 0: attention dropout at that rate under the mask of (seed, head, edge)
+    (maxk_gat_attention_heads_dropout; edge_dropout_heads has the contract): out sums
+    alpha * d * value, the statistics stay those of the undropped softmax."""
     D = int(dim_origin)
     H, num_rows, num_cols, E = _gat_heads_operands(indptr, indices, s_dst, s_src)
     _, cols2, k = _heads_operands(indptr, indices, cbsr_val, cbsr_idx, None, validate, D)
@@ -684,10 +688,47 @@ def gat_attention_heads(indptr: torch.Tensor, indices: torch.Tensor, s_dst: torc
     row_max = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
     row_sum = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
     shape = (num_rows, num_cols, E, D, k, H, chunk)
-    _launch_ws(dev, "maxk_gat_attention_heads", "maxk_gat_attention_heads_workspace_size", shape,
-               (_ptr(indptr), _ptr(indices), _ptr(s_dst), _ptr(s_src), float(negative_slope),
-                _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), _ptr(row_max), _ptr(row_sum), *shape))
+    args = (_ptr(indptr), _ptr(indices), _ptr(s_dst), _ptr(s_src), float(negative_slope),
+            _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), _ptr(row_max), _ptr(row_sum), *shape)
+    if dropout > 0:
+        _launch_ws(dev, "maxk_gat_attention_heads_dropout",
+                   "maxk_gat_attention_heads_dropout_workspace_size", shape,
+                   args + _dropout_args(dropout, seed))
+    else:
+        _dropout_args(dropout, seed)
+        _launch_ws(dev, "maxk_gat_attention_heads", "maxk_gat_attention_heads_workspace_size",
+                   shape, args)
     return out, row_max, row_sum
+
+
+def _dropout_args(p, seed) -> Tuple[float, int]:
+    """(p, seed) as the C ABI takes them: 0 <= p < 1, seed an unsigned 64-bit integer."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise RuntimeError(f"dropout must be in [0, 1), got {p}")
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise RuntimeError("seed must be in [0, 2^64)")
+    return p, seed
+
+
+def edge_dropout_heads(w: torch.Tensor, p: float, seed: int,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[H, E] = w[H, E] * d: attention dropout of head-major edge weights
+    (maxk_edge_dropout_heads).  d[h, e] is 0 where word h & 3 of Philox4x32-10(counter
+    (e, 0, h >> 2, 0), key seed) is below floor(p * 2^32), else float32(1 / (1 - p)): a pure
+    function of (seed, h, e) that no kernel stores, so the same call on the gradient is this
+    one's backward and the fused attention (gat_attention_heads(dropout=, seed=)) applies the
+    same mask.  out may be w.  0 <= p < 1."""
+    _need(w, "w", torch.float32)
+    if w.dim() != 2 or not 1 <= w.shape[0] <= MAX_HEADS:
+        raise RuntimeError(f"w must be [H, num_e] with 1 <= H <= {MAX_HEADS}")
+    p, seed = _dropout_args(p, seed)
+    dev = w.device
+    out = _heads_out(out, tuple(w.shape), dev, "[H, num_e]")
+    _launch(dev, "maxk_edge_dropout_heads", _ptr(w), _ptr(out), w.shape[0], w.shape[1], p, seed,
+            _stream(dev))
+    return out
 
 
 def gat_edge_alpha_heads(indptr: torch.Tensor, indices: torch.Tensor, s_dst: torch.Tensor,
@@ -743,7 +784,8 @@ def gat_attention_heads_backward(indptr: torch.Tensor, indices: torch.Tensor,
                                  cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor,
                                  out: torch.Tensor, row_max: torch.Tensor, row_sum: torch.Tensor,
                                  grad_output: torch.Tensor, negative_slope: float = 0.2,
-                                 chunk: int = 0, validate: Optional[bool] = None, plan=None):
+                                 chunk: int = 0, validate: Optional[bool] = None, plan=None,
+                                 dropout: float = 0.0, seed: int = 0):
     """(grad_s_dst [H, num_rows], grad_s_src [H, num_cols], grad_cbsr [num_cols, k]) of
     gat_attention_heads from its three results and the gradient of `out`, in one walk of the
     graph (maxk_gat_attention_heads_backward): what gat_edge_alpha_heads, edge_weight_grad_heads,
@@ -751,7 +793,8 @@ def gat_attention_heads_backward(indptr: torch.Tensor, indices: torch.Tensor,
     tensor allocated.  The row sum of the softmax backward is taken as the dot product of
     out[h, r] and grad_output[h, r], so `out` must be the forward's.  Uses the graph's transpose
     plan (cached per `indices`, or `plan=` from transpose_plan()).  Bitwise repeatable; the same
-    operand checks as gat_attention_heads."""
+    operand checks as gat_attention_heads.  dropout, seed: those of the forward that produced
+    `out` (maxk_gat_attention_heads_dropout_backward); the row sum is still that dot product."""
     _need(grad_output, "grad_output", torch.float32)
     _need(out, "out", torch.float32)
     if grad_output.dim() != 3 or not 1 <= grad_output.shape[0] <= MAX_HEADS:
@@ -774,12 +817,17 @@ def gat_attention_heads_backward(indptr: torch.Tensor, indices: torch.Tensor,
     g_src = torch.empty(H, num_cols, dtype=torch.float32, device=dev)
     g_cbsr = torch.empty(num_cols, k, dtype=torch.float32, device=dev)
     shape = (num_rows, num_cols, E, D, k, H, chunk)
-    _launch_ws(dev, "maxk_gat_attention_heads_backward",
-               "maxk_gat_attention_heads_backward_workspace_size", shape,
-               (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(s_dst),
-                _ptr(s_src), float(negative_slope), _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out),
-                _ptr(row_max), _ptr(row_sum), _ptr(grad_output), _ptr(g_dst), _ptr(g_src),
-                _ptr(g_cbsr), *shape))
+    args = (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(s_dst), _ptr(s_src),
+            float(negative_slope), _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), _ptr(row_max),
+            _ptr(row_sum), _ptr(grad_output), _ptr(g_dst), _ptr(g_src), _ptr(g_cbsr), *shape)
+    if dropout > 0:
+        _launch_ws(dev, "maxk_gat_attention_heads_dropout_backward",
+                   "maxk_gat_attention_heads_dropout_backward_workspace_size", shape,
+                   args + _dropout_args(dropout, seed))
+    else:
+        _dropout_args(dropout, seed)
+        _launch_ws(dev, "maxk_gat_attention_heads_backward",
+                   "maxk_gat_attention_heads_backward_workspace_size", shape, args)
     return g_dst, g_src, g_cbsr
 
 

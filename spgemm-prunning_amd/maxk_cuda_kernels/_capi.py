@@ -86,6 +86,22 @@ SIGNATURES = {
                                                          _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                                          _i64, _i64, _i64, _i32, _i32, _i32, _i32,
                                                          _p, _sz, _p]),
+    "maxk_edge_dropout_heads": (ctypes.c_int, [_p, _p, _i32, _i64, ctypes.c_float,
+                                               ctypes.c_uint64, _p]),
+    "maxk_gat_attention_heads_dropout_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32,
+                                                              _i32]),
+    "maxk_gat_attention_heads_dropout": (ctypes.c_int, [_p, _p, _p, _p, ctypes.c_float, _p, _p, _p,
+                                                        _p, _p, _i64, _i64, _i64, _i32, _i32, _i32,
+                                                        _i32, ctypes.c_float, ctypes.c_uint64, _p,
+                                                        _sz, _p]),
+    "maxk_gat_attention_heads_dropout_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32,
+                                                                       _i32, _i32, _i32]),
+    "maxk_gat_attention_heads_dropout_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p,
+                                                                 ctypes.c_float, _p, _p, _p, _p,
+                                                                 _p, _p, _p, _p, _p, _i64, _i64,
+                                                                 _i64, _i32, _i32, _i32, _i32,
+                                                                 ctypes.c_float, ctypes.c_uint64,
+                                                                 _p, _sz, _p]),
     "maxk_sspmm_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
     "maxk_sspmm_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                            _i32, _i32, _i32, _p, _sz, _p]),

@@ -40,7 +40,8 @@ import torch.nn as nn
 from torch.autograd import Function
 
 import maxk_cuda_kernels as mk
-from maxk_spgemm_function import maxk_gat_attention_heads, maxk_spgemm, maxk_spgemm_heads
+from maxk_spgemm_function import (maxk_edge_dropout_heads, maxk_gat_attention_heads, maxk_spgemm,
+                                  maxk_spgemm_heads)
 
 
 def _clamped(graph, name: str) -> torch.Tensor:
@@ -95,19 +96,24 @@ class CSRGraph:
                                  dim, row_div)
 
     def attend_heads(self, topk_values, topk_indices, dim: int, s_dst, s_src,
-                     negative_slope: float = 0.2, backward: str = "rebuilt"):
+                     negative_slope: float = 0.2, backward: str = "rebuilt",
+                     dropout: float = 0.0, seed: int = 0):
         """[H, V, dim]: the attention aggregation of H GAT heads from their scores s_dst [H, V]
         and s_src [H, V] with the softmax inside the walk (maxk_gat_attention_heads): what
         gat_edge_softmax_heads followed by aggregate_heads give, without alpha [H, E] stored.
         backward: "rebuilt" (alpha as a transient of the backward) or "fused" (one walk, no
-        [H, E] tensor in the backward either); MAXK_HEADS_ATTN_BWD=fused|rebuilt overrides it."""
+        [H, E] tensor in the backward either); MAXK_HEADS_ATTN_BWD=fused|rebuilt overrides it.
+        dropout, seed: attention dropout inside the walk under the mask of (seed, head, edge)
+        (mk.edge_dropout_heads has the contract); only the two numbers are kept for the
+        backward, which recomputes the mask."""
         if backward not in ("rebuilt", "fused"):
             raise ValueError(f'backward must be "rebuilt" or "fused", got {backward!r}')
         forced = os.environ.get("MAXK_HEADS_ATTN_BWD", "")
         if forced in ("fused", "rebuilt"):
             backward = forced
         return maxk_gat_attention_heads(self.indptr, self.indices, s_dst, s_src, topk_values,
-                                        topk_indices, dim, negative_slope, backward)
+                                        topk_indices, dim, negative_slope, backward, dropout,
+                                        seed)
 
 
 class MaxK(Function):
@@ -426,6 +432,23 @@ def gat_edge_softmax(graph: CSRGraph, s_dst: torch.Tensor, s_src: torch.Tensor,
     return GATEdgeSoftmax.apply(graph.indptr, graph.indices, s_dst, s_src, negative_slope)
 
 
+def _check_attn_drop(p) -> float:
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"attn_drop must be in [0, 1), got {p}")
+    return p
+
+
+def attn_seed_of(attn_seed: Optional[int]) -> int:
+    """The seed of one forward's attention-dropout mask: attn_seed as given, or a fresh 63-bit
+    draw from torch's default CPU generator (reproducible under torch.manual_seed, and no device
+    synchronisation).  The seed reaches the kernels by value: a forward captured into a graph
+    replays the mask it was captured with."""
+    if attn_seed is not None:
+        return int(attn_seed)
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+
+
 def gat_edge_softmax_heads(graph: CSRGraph, s_dst: torch.Tensor, s_src: torch.Tensor,
                            negative_slope: float = 0.2) -> torch.Tensor:
     """alpha [H, E] float32 of H GAT heads from their scores s_dst [H, V], s_src [H, V]: one
@@ -450,11 +473,16 @@ class MaxKGATConv(nn.Module):
     coefficients come from them in one HIP pass (gat_edge_softmax).  Gradients reach fc.weight
     and both attention vectors, x_sparse through the scores and topk_values through the
     aggregation (its feature backward, edge_weight_grad and the softmax backward).  The
-    reference has no GAT: there is no reference_compat."""
+    reference has no GAT: there is no reference_compat.
+
+    attn_drop: the GAT's dropout of alpha between the softmax and the aggregation, in training
+    mode, through mk.edge_dropout_heads at one head (see MaxKMultiHeadGATConv);
+    forward(..., attn_seed=) fixes the mask's seed."""
 
     def __init__(self, in_feats: int, out_feats: int, negative_slope: float = 0.2,
-                 bias: bool = True, activation=None):
+                 bias: bool = True, activation=None, attn_drop: float = 0.0):
         super().__init__()
+        self.attn_drop = _check_attn_drop(attn_drop)
         self.in_feats, self.out_feats = in_feats, out_feats
         self.negative_slope = float(negative_slope)
         self.fc = nn.Linear(in_feats, out_feats, bias=False)
@@ -468,11 +496,15 @@ class MaxKGATConv(nn.Module):
             nn.init.xavier_normal_(self.attn_src.view(1, -1), gain=gain)
             nn.init.xavier_normal_(self.attn_dst.view(1, -1), gain=gain)
 
-    def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices):
+    def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices,
+                attn_seed: Optional[int] = None):
         # attn . fc(x) = x . (fc.weight^T attn): both scores from one [V, in] x [in, 2] product
         v = self.fc.weight.t() @ torch.stack((self.attn_dst, self.attn_src), 1)
         s = x_sparse @ v
         alpha = gat_edge_softmax(graph, s[:, 0], s[:, 1], self.negative_slope)
+        if self.training and self.attn_drop > 0:
+            alpha = maxk_edge_dropout_heads(alpha.view(1, -1), self.attn_drop,
+                                            attn_seed_of(attn_seed)).view(-1)
         agg = graph.aggregate(topk_values, topk_indices, self.in_feats, values=alpha,
                               row_div=None)
         rst = linear(agg, self.fc)
@@ -502,12 +534,25 @@ class MaxKMultiHeadGATConv(nn.Module):
     transient in the backward.  MAXK_HEADS_ATTN=fused|stored overrides the argument.
     attention_backward="fused" (with the fused attention only; the default is "rebuilt") runs
     that backward as one walk without alpha (CSRGraph.attend_heads(backward="fused"));
-    MAXK_HEADS_ATTN_BWD=fused|rebuilt overrides the argument."""
+    MAXK_HEADS_ATTN_BWD=fused|rebuilt overrides the argument.
+
+    attn_drop: the GAT's attention dropout, in training mode: every alpha_hvu is zeroed with
+    probability attn_drop and the kept ones scaled by 1 / (1 - attn_drop), after the softmax's
+    normalisation.  The mask is a pure function of (seed, head, edge) that every kernel
+    recomputes (mk.edge_dropout_heads has the contract) and nothing stores, so it works with all
+    three combinations of attention / attention_backward and adds no [H, E] tensor to the fused
+    ones.  The stored path keeps two [H, E] tensors for its backward, alpha for the softmax
+    backward and the dropped alpha for the aggregation: a known limit.  forward(...,
+    attn_seed=None) draws a fresh seed per call (attn_seed_of); an int is used as given.  In
+    eval() or with attn_drop == 0 the layer computes bitwise what it computes without the
+    argument."""
 
     def __init__(self, in_feats: int, out_feats: int, num_heads: int,
                  negative_slope: float = 0.2, bias: bool = True, activation=None,
-                 attention: str = "stored", attention_backward: str = "rebuilt"):
+                 attention: str = "stored", attention_backward: str = "rebuilt",
+                 attn_drop: float = 0.0):
         super().__init__()
+        self.attn_drop = _check_attn_drop(attn_drop)
         if attention not in ("stored", "fused"):
             raise ValueError(f'attention must be "stored" or "fused", got {attention!r}')
         if attention_backward not in ("rebuilt", "fused"):
@@ -542,8 +587,11 @@ class MaxKMultiHeadGATConv(nn.Module):
         forced = os.environ.get("MAXK_HEADS_ATTN_BWD", "")
         return forced if forced in ("fused", "rebuilt") else self.attention_backward
 
-    def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices):
+    def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices,
+                attn_seed: Optional[int] = None):
         H, O = self.num_heads, self.out_feats
+        p = self.attn_drop if self.training else 0.0
+        seed = attn_seed_of(attn_seed) if p > 0 else 0
         W = self.fc.weight.view(H, O, self.in_feats)
         # attn[h] . W_h x = x . (W_h^T attn[h]): every head's two scores from one product
         v = torch.cat((torch.einsum("hoi,ho->ih", W, self.attn_dst),
@@ -551,9 +599,11 @@ class MaxKMultiHeadGATConv(nn.Module):
         s = (x_sparse @ v).t().contiguous()                               # [2H, V]
         if self.attention_mode() == "fused":
             agg = graph.attend_heads(topk_values, topk_indices, self.in_feats, s[:H], s[H:],
-                                     self.negative_slope, self.attention_backward_mode())
+                                     self.negative_slope, self.attention_backward_mode(), p,
+                                     seed)
         else:
             alpha = gat_edge_softmax_heads(graph, s[:H], s[H:], self.negative_slope)
+            alpha = maxk_edge_dropout_heads(alpha, p, seed)
             agg = graph.aggregate_heads(topk_values, topk_indices, self.in_feats, alpha)
         rst = torch.bmm(agg, W.transpose(1, 2)).transpose(0, 1)          # [V, H, out]
         if self.bias is not None:

@@ -402,11 +402,17 @@ class MaxKGATAttentionHeadsFunction(Function):
     well and runs one maxk_cuda_kernels.gat_attention_heads_backward call instead: no tensor of
     H * E elements in the backward either.  It falls back to the rebuilt backward when not all
     three gradients are needed, when the table is too large for the entry
-    (maxk_cuda_kernels.HEADS_MAX_COLS) and when MAXK_BWD_MODE forces a backward mode."""
+    (maxk_cuda_kernels.HEADS_MAX_COLS) and when MAXK_BWD_MODE forces a backward mode.
+
+    dropout, seed (a tenth and eleventh argument, default 0.0 and 0): attention dropout under
+    the mask of (seed, head, edge) that maxk_cuda_kernels.edge_dropout_heads documents.  Only
+    the two numbers are kept: the forward walk evaluates the mask, the fused backward evaluates
+    it again in its one call, and the rebuilt backward masks the rebuilt coefficients once for
+    the feature gradient and the weight gradient before the softmax backward."""
 
     @staticmethod
     def forward(ctx, graph_indptr, graph_indices, s_dst, s_src, topk_values, topk_indices,
-                dim_origin, negative_slope, backward="rebuilt"):
+                dim_origin, negative_slope, backward="rebuilt", dropout=0.0, seed=0):
         _require_kernels()
         if backward not in ("rebuilt", "fused"):
             raise ValueError(f'backward must be "rebuilt" or "fused", got {backward!r}')
@@ -416,7 +422,9 @@ class MaxKGATAttentionHeadsFunction(Function):
         sel = sel.contiguous()
         sd, ss = _f32_act(s_dst), _f32_act(s_src)
         out, row_max, row_sum = maxk_cuda_kernels.gat_attention_heads(
-            indptr, indices, sd, ss, vals, sel, int(dim_origin), float(negative_slope))
+            indptr, indices, sd, ss, vals, sel, int(dim_origin), float(negative_slope),
+            dropout=float(dropout), seed=int(seed))
+        ctx.drop = (float(dropout), int(seed))
         V, k = vals.shape
         ctx.bwd_mode = maxk_cuda_kernels.graph_only_mode(k, indices.numel(), V)
         ctx.slope = float(negative_slope)
@@ -439,20 +447,25 @@ class MaxKGATAttentionHeadsFunction(Function):
         H = sd.shape[0]
         need_s = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         grad_sd = grad_ss = grad_tv = None
+        p, seed = ctx.drop
         if ctx.fused_bwd and all(ctx.needs_input_grad[2:5]):
             grad_sd, grad_ss, grad_tv = maxk_cuda_kernels.gat_attention_heads_backward(
                 indptr, indices, sd, ss, vals, sel, ctx.saved_tensors[8], row_max, row_sum, g,
-                ctx.slope)
+                ctx.slope, dropout=p, seed=seed)
             return (None, None, grad_sd.to(ctx.dtypes[0]), grad_ss.to(ctx.dtypes[1]), grad_tv,
-                    None, None, None, None)
+                    None, None, None, None, None, None)
         alpha = maxk_cuda_kernels.gat_edge_alpha_heads(indptr, indices, sd, ss, row_max, row_sum,
                                                        ctx.slope)
         if need_s:
             grad_w = maxk_cuda_kernels.edge_weight_grad_heads(indptr, indices, vals, sel, g)
+            if p > 0:  # the gradient of the dropped coefficients back through the mask
+                maxk_cuda_kernels.edge_dropout_heads(grad_w, p, seed, out=grad_w)
             grad_sd, grad_ss = maxk_cuda_kernels.gat_edge_softmax_heads_backward(
                 indptr, indices, sd, ss, alpha, grad_w, ctx.slope)
             del grad_w
             grad_sd, grad_ss = grad_sd.to(ctx.dtypes[0]), grad_ss.to(ctx.dtypes[1])
+        if p > 0 and ctx.needs_input_grad[4]:  # the softmax backward above took the undropped
+            maxk_cuda_kernels.edge_dropout_heads(alpha, p, seed, out=alpha)
         if ctx.needs_input_grad[4] and maxk_cuda_kernels.heads_backward_route(
                 sel.shape[1], indices.numel(), sel.shape[0], indptr.numel() - 1, H) == "heads":
             grad_tv = maxk_cuda_kernels.sspmm_backward_heads(indptr, indices, alpha, g, sel)
@@ -463,20 +476,51 @@ class MaxKGATAttentionHeadsFunction(Function):
                 grad_tv = part if grad_tv is None else grad_tv.add_(part)
         del alpha
         return (None, None, grad_sd if ctx.needs_input_grad[2] else None,
-                grad_ss if ctx.needs_input_grad[3] else None, grad_tv, None, None, None, None)
+                grad_ss if ctx.needs_input_grad[3] else None, grad_tv, None, None, None, None,
+                None, None)
+
+
+class MaxKEdgeDropoutHeadsFunction(Function):
+    """Attention dropout of head-major edge weights: apply(w [H, E], p, seed) -> w * d, d the mask
+    of maxk_cuda_kernels.edge_dropout_heads.  It saves (p, seed) and no tensor: the backward is
+    the same call on the gradient, which recomputes the mask."""
+
+    @staticmethod
+    def forward(ctx, w, p, seed):
+        _require_kernels()
+        ctx.drop = (float(p), int(seed))
+        ctx.w_dtype = w.dtype
+        return maxk_cuda_kernels.edge_dropout_heads(_f32_act(w), *ctx.drop)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        g = grad_output.contiguous()
+        if g.dtype != torch.float32:
+            g = g.float()
+        return maxk_cuda_kernels.edge_dropout_heads(g, *ctx.drop).to(ctx.w_dtype), None, None
+
+
+def maxk_edge_dropout_heads(w, p, seed):
+    """w [H, E] * d under the attention-dropout mask of (seed, head, edge), rate p
+    (MaxKEdgeDropoutHeadsFunction); p == 0 returns w itself."""
+    if p == 0:
+        return w
+    return MaxKEdgeDropoutHeadsFunction.apply(w, p, seed)
 
 
 def maxk_gat_attention_heads(graph_indptr, graph_indices, s_dst, s_src, topk_values,
-                             topk_indices, dim_origin, negative_slope=0.2, backward="rebuilt"):
+                             topk_indices, dim_origin, negative_slope=0.2, backward="rebuilt",
+                             dropout=0.0, seed=0):
     """[H, V, dim_origin] = sum over a row's edges of softmax(leaky_relu(s_dst[h, row] +
     s_src[h, col])) * scatter(topk)[col], for the H heads of one CSR graph, without the
     coefficients [H, E] being stored; gradients for s_dst, s_src and topk_values
     (MaxKGATAttentionHeadsFunction).  backward: "rebuilt" (the coefficients as a transient and
-    the stored path's passes) or "fused" (one gat_attention_heads_backward call)."""
+    the stored path's passes) or "fused" (one gat_attention_heads_backward call).  dropout,
+    seed: attention dropout inside the walk, the mask recomputed by each backward."""
     _require_kernels()
     return MaxKGATAttentionHeadsFunction.apply(graph_indptr, graph_indices, s_dst, s_src,
                                                topk_values, topk_indices, dim_origin,
-                                               negative_slope, backward)[0]
+                                               negative_slope, backward, dropout, seed)[0]
 
 
 class MaxKSpmmWrapper:

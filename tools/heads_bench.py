@@ -39,6 +39,14 @@ within every iteration so all of them see the same clocks and cache state:
                         attention stored, fused with the rebuilt backward and fused with the
                         fused backward, with the peak memory of one step of each
 
+  attention_dropout_fwd / attention_fwd   mk.gat_attention_heads with dropout = 0.6 against
+                        without: the mask's cost in the walk            (--pairs attention_dropout)
+  attention_dropout_bwd / attention_bwd   mk.gat_attention_heads_backward likewise
+  step_stored / step_fused_rebuilt / step_fused_fused   the layer's forward plus backward with
+                        attn_drop = 0.6 in its three modes, against step_torch_dropout: the
+                        stored path with torch.nn.functional.dropout on alpha, what a user would
+                        write without the mask entries; the peak memory of one step of each
+
 It reports the medians, the ratio heads / calls of each pair, and the run-to-run spread of the
 single-head baselines in this run, (max - min) / median over the iterations: the heads kernel
 counts as faster only where 1 - ratio exceeds that spread.  For the feature gradient it also
@@ -49,6 +57,7 @@ timed.  Writes one JSON file and prints it.
                               [--pairs forward,edge_grad,feat_grad]
   python tools/heads_bench.py --pairs softmax,layer --heads 1,2,4,8 --out FILE
   python tools/heads_bench.py --pairs attention --heads 1,2,4,8 --out FILE
+  python tools/heads_bench.py --pairs attention_dropout --heads 1,2,4,8 --out FILE
 """
 import argparse
 import json
@@ -517,6 +526,123 @@ def run_attention_bwd(name, k, D, H, iters, warmup, seed, dev, slope=0.2):
     return r
 
 
+def run_attention_dropout(name, k, D, H, iters, warmup, seed, dev, slope=0.2, p=0.6):
+    """The mask's cost: mk.gat_attention_heads and mk.gat_attention_heads_backward with
+    dropout = p against the same calls without, alternating inside every iteration; then the
+    layer's training step with attn_drop = p in its three modes against the stored path with
+    torch.nn.functional.dropout on alpha, and the peak memory of one step of each."""
+    import maxk_layers as ML
+    V = bench.maxk_graph.PRESETS[name]["V"]
+    row_ptr, col = _graph(name, seed, dev)
+    E = col.numel()
+    gen = torch.Generator(device=dev).manual_seed(987)
+    sd = torch.randn(H, V, generator=gen, device=dev)
+    ss = torch.randn(H, V, generator=gen, device=dev)
+    cv, ci = mk.topk_cbsr(torch.rand(V, D, generator=gen, device=dev), k)
+    G = torch.randn(H, V, D, generator=gen, device=dev)
+    y = torch.empty(H, V, D, device=dev)
+    plan = mk.transpose_plan(col, V)
+    mseed = 0x5EED0001
+    fw = {False: mk.gat_attention_heads(row_ptr, col, sd, ss, cv, ci, D, slope, validate=True),
+          True: mk.gat_attention_heads(row_ptr, col, sd, ss, cv, ci, D, slope, validate=False,
+                                       dropout=p, seed=mseed)}
+    keep = {}
+
+    def fwd(drop):
+        mk.gat_attention_heads(row_ptr, col, sd, ss, cv, ci, D, slope, out=y, validate=False,
+                               dropout=p if drop else 0.0, seed=mseed)
+
+    def bwd(drop):
+        keep[drop] = mk.gat_attention_heads_backward(
+            row_ptr, col, sd, ss, cv, ci, *fw[drop], G, slope, validate=False, plan=plan,
+            dropout=p if drop else 0.0, seed=mseed)
+
+    ops = (("attention_dropout_fwd", lambda: fwd(True)), ("attention_fwd", lambda: fwd(False)),
+           ("attention_dropout_bwd", lambda: bwd(True)), ("attention_bwd", lambda: bwd(False)))
+    for _ in range(warmup):
+        for _, fn in ops:
+            fn()
+    torch.cuda.synchronize()
+    ts = {n: [] for n, _ in ops}
+    for _ in range(iters):
+        for n, fn in ops:
+            ts[n].append(timed(fn))
+    s = {n: summary(t) for n, t in ts.items()}
+    r = dict(kind="attention_dropout", graph=name, V=V, E=E, D=D, k=k, H=H, p=p, **s)
+    r["dropped_fraction_of_out_zero"] = float((fw[True][0] == 0).float().mean()
+                                              - (fw[False][0] == 0).float().mean())
+    for what in ("fwd", "bwd"):
+        ratio = s[f"attention_dropout_{what}"]["median_ms"] / s[f"attention_{what}"]["median_ms"]
+        spread = s[f"attention_{what}"]["spread"]
+        r[f"ratio_attention_dropout_{what}_to_plain"] = round(ratio, 4)
+        r[f"attention_dropout_{what}_slower"] = bool(ratio - 1.0 > spread)
+    keep.clear()
+    del fw, G, y
+    torch.cuda.empty_cache()
+
+    graph = ML.CSRGraph(row_ptr, col)
+    torch.manual_seed(7)
+    conv = ML.MaxKMultiHeadGATConv(D, D // H, H, attn_drop=p).to(dev)
+    xs, vals, idx = ML.maxk(torch.rand(V, D, device=dev), k)
+    xs = xs.detach().requires_grad_(True)
+    vals = vals.detach().requires_grad_(True)
+    modes = {"stored": ("stored", "rebuilt"), "fused_rebuilt": ("fused", "rebuilt"),
+             "fused_fused": ("fused", "fused"), "torch_dropout": None}
+
+    def torch_dropout_forward():  # MaxKMultiHeadGATConv.forward, stored, with F.dropout on alpha
+        O = conv.out_feats
+        W = conv.fc.weight.view(H, O, D)
+        v = torch.cat((torch.einsum("hoi,ho->ih", W, conv.attn_dst),
+                       torch.einsum("hoi,ho->ih", W, conv.attn_src)), 1)
+        sc = (xs @ v).t().contiguous()
+        alpha = ML.gat_edge_softmax_heads(graph, sc[:H], sc[H:], conv.negative_slope)
+        alpha = torch.nn.functional.dropout(alpha, p, training=True)
+        agg = graph.aggregate_heads(vals, idx, D, alpha)
+        return torch.bmm(agg, W.transpose(1, 2)).transpose(0, 1) + conv.bias
+
+    def step(mode):
+        conv.zero_grad(set_to_none=True)
+        xs.grad = vals.grad = None
+        if modes[mode] is None:
+            torch_dropout_forward().sum().backward()
+        else:
+            conv.attention, conv.attention_backward = modes[mode]
+            conv(graph, xs, vals, idx).sum().backward()
+
+    saved = {v: os.environ.pop(v, None) for v in ("MAXK_HEADS_ATTN", "MAXK_HEADS_ATTN_BWD")}
+    try:
+        for _ in range(warmup):
+            for mode in modes:
+                step(mode)
+        torch.cuda.synchronize()
+        tl = {mode: [] for mode in modes}
+        for _ in range(iters):
+            for mode in modes:
+                tl[mode].append(timed(lambda: step(mode)))
+        for mode in modes:  # the peak of one step, the other modes' buffers released
+            conv.zero_grad(set_to_none=True)
+            xs.grad = vals.grad = None
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            step(mode)
+            torch.cuda.synchronize()
+            r[f"step_{mode}_peak_bytes"] = int(torch.cuda.max_memory_allocated())
+            r[f"step_{mode}_peak_over_resident_bytes"] = int(torch.cuda.max_memory_allocated()
+                                                             - base)
+    finally:
+        for v, x in saved.items():
+            if x is not None:
+                os.environ[v] = x
+    sl = {f"step_{mode}": summary(t) for mode, t in tl.items()}
+    r.update(sl)
+    for mode in ("stored", "fused_rebuilt", "fused_fused"):
+        r[f"ratio_step_{mode}_to_torch_dropout"] = round(
+            sl[f"step_{mode}"]["median_ms"] / sl["step_torch_dropout"]["median_ms"], 4)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--graphs", default="reddit:16,products:32")
@@ -548,6 +674,9 @@ def main():
             if "attention_bwd" in asked:
                 rs.append(run_attention_bwd(name, int(k), args.dim, H, args.iters, args.warmup,
                                             args.seed, dev))
+            if "attention_dropout" in asked:
+                rs.append(run_attention_dropout(name, int(k), args.dim, H, args.iters,
+                                                args.warmup, args.seed, dev))
             if "layer" in asked and H >= 2:
                 rs.append(run_layer(name, int(k), args.dim, H, args.iters, args.warmup,
                                     args.seed, dev))
