@@ -587,6 +587,84 @@ int maxk_gat_attention_heads_dropout_backward(
     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Fused multi-head dot-product attention on CBSR keys: the scaled dot-product score and its edge
+ * softmax inside the aggregation walk,
+ *   l_he = scale * sum_l cbsr_val[c,l] * q[h, r, cbsr_idx[c,l]]      e in row r, c = col_idx[e]
+ *   m_hr = max_e l_he,   z_hr = sum_e exp(l_he - m_hr),   alpha[h,e] = exp(l_he - m_hr) / z_hr
+ *   out[h, r, cbsr_idx[c,l]] += alpha[h,e] * cbsr_val[c,l]
+ * -- maxk_edge_weight_grad_heads with grad_out := q, the scale, num_heads edge softmaxes and
+ * maxk_spgemm_forward_heads in one walk of the graph.  q is f32 [num_heads, num_rows,
+ * dim_origin], the query of destination r already mapped into the feature space
+ * (q_r . k_c = x_r^T W_q^T W_k x_c = q[h, r] . x_c, and x_c is the CBSR row); selectors
+ * >= dim_origin add nothing.  Neither the logits nor alpha [num_heads, num_e] exist anywhere,
+ * not in an output and not in the workspace: the outputs are out [num_heads, num_rows,
+ * dim_origin] and the row statistics row_max = m and row_sum = z, f32 [num_heads, num_rows], from
+ * which maxk_dot_edge_alpha_heads rebuilds
+ *   w[h,e] = exp(l_he - row_max[h,r]) / row_sum[h,r]          f32 [num_heads, num_e], CSR order
+ * for the backward (one record gather per edge for all heads, no reductions over edges).  The
+ * reference has no counterpart.  Head-major layout as above; 1 <= num_heads <= MAXK_MAX_HEADS,
+ * any value, one head included.  There is no row_div: attention rows are normalised by z.
+ * Per row piece the kernel stages the num_heads rows scale * q[h, r, :] in LDS, sweeps the
+ *   records once for the piece's maximum per head, then gathers each record again (from the
+ *   caches) with p = exp(l - m_piece), l recomputed by the same device functions, summing
+ *   p * value in LDS and p per head: nothing is rescaled per edge.  A row inside one work item is
+ *   stored as sum / z; a hub row cut over items leaves unnormalised pieces with their (m, z),
+ *   merged in item order: m = max m_i, each piece scaled by exp(m_i - m), one division.  No
+ *   global and no LDS atomics.
+ * Shapes: any 1 <= dim_k <= dim_origin <= 256 (dim_k % 4 != 0, odd dim_origin, dim_k > 64), any
+ *   num_rows != num_cols; num_e == 0 writes zeros to all of out and both statistics (the alpha
+ *   entry launches nothing); a table past 2^24 columns or 4 GiB of packed records is rejected
+ *   with MAXK_ERR_INVALID.  scale: finite and > 0.
+ * Writes: every element of out, row_max and row_sum (the alpha entry: every edge of w).  A row
+ *   without edges gives exact zeros in all three; a column of out that no edge of the row selects
+ *   is exactly 0.
+ * Numerics (tests/dot_attention_ref.py; u = 2^-24): a logit is within
+ *   d = (n_c + 8) * u * scale * sum|value * q| + 2^-149 of exact, n_c its number of kept slots;
+ *   each weight is within (n_r + 24 + 16 A_r) * u * alpha + 2 d * alpha + (n_r + 16) * 2^-149,
+ *   A_r = max|l| -- the edge softmax's bound, 8 u for a cut row's merge and the logit error
+ *   carried through the exponent -- and out within that carried through the sum plus
+ *   (n + 8) * (u * sum|alpha * value| + 2^-149), n the element's number of addends.  row_max is
+ *   within the logit bound, row_sum within the weight bound's relative part.
+ * Non-finite values follow the IEEE evaluation of the formulas: a row with a NaN or +Inf logit is
+ *   NaN wherever it has an addend (and 0 elsewhere), a -Inf logit contributes exactly 0, a row
+ *   of only -Inf is NaN wherever it has an addend; a NaN in q[h, r, j] at a column j that none of
+ *   row r's neighbours selects reaches nothing (maxk_edge_weight_grad_heads' rule).
+ * Bitwise repeatable for equal arguments whatever the workspace held (every sum's order is
+ *   fixed by the graph, chunk_edges, dim_k and num_heads); head h's slices of the three outputs
+ *   do not depend, bitwise, on the other heads' q.
+ * Memory, as the top comment: the workspace (packed records, per-head slabs and statistics of
+ *   the cut rows -- the only term that grows with num_heads * num_e; for the alpha entry the
+ *   records alone) is exactly the queried size, 256-B aligned, and may hold anything; a shorter
+ *   one is rejected ("workspace too small") on the host before any launch; nothing is written
+ *   outside the outputs and the workspace, inputs are never written; no allocation, copy or
+ *   synchronisation.  The size is non-decreasing in num_e.
+ * Argument errors (num_heads outside [1, MAXK_MAX_HEADS], a null pointer, negative sizes, scale
+ *   not finite or <= 0, k / D range): MAXK_ERR_INVALID with a message naming the argument,
+ *   before any launch.
+ * chunk_edges: tokens per wavefront work item, 0 = the auto rule, sized for the waves a CU holds
+ *   beside the staged query rows.
+ * ------------------------------------------------------------------------- */
+size_t maxk_dot_attention_heads_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                               int32_t dim_origin, int32_t dim_k,
+                                               int32_t num_heads, int32_t chunk_edges);
+int maxk_dot_attention_heads(const int32_t *row_ptr, const int32_t *col_idx, const float *q,
+                             float scale, const float *cbsr_val, const uint8_t *cbsr_idx,
+                             float *out, float *row_max, float *row_sum, int64_t num_rows,
+                             int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                             int32_t num_heads, int32_t chunk_edges, void *workspace,
+                             size_t workspace_bytes, void *stream);
+size_t maxk_dot_edge_alpha_heads_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                                int32_t dim_origin, int32_t dim_k,
+                                                int32_t num_heads, int32_t chunk_edges);
+int maxk_dot_edge_alpha_heads(const int32_t *row_ptr, const int32_t *col_idx, const float *q,
+                              float scale, const float *cbsr_val, const uint8_t *cbsr_idx,
+                              const float *row_max, const float *row_sum, float *w,
+                              int64_t num_rows, int64_t num_cols, int64_t num_e,
+                              int32_t dim_origin, int32_t dim_k, int32_t num_heads,
+                              int32_t chunk_edges, void *workspace, size_t workspace_bytes,
+                              void *stream);
+
+/* ---------------------------------------------------------------------------
  * Backward outer-product sampled SpMM (SSpMM):
  *   grad_cbsr[c,l] = sum_{e=(r->c)} edge_val[e] * grad_out[r, cbsr_idx[c,l]] / row_div[r]
  *                  = (A^T diag(1/row_div) G)[c, cbsr_idx[c,l]]     (from the CSR of A)

@@ -585,7 +585,7 @@ int check_sizes(int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t chunk
     MAXK_REQUIRE(chunk_edges >= 0, "chunk_edges must be >= 0");
     return MAXK_OK;
 }
-int check_slope(float slope) {
+inline int check_slope(float slope) {  // inline: the dot-product attention has no slope
     MAXK_REQUIRE(slope >= 0.f && slope <= 1.f, "negative_slope must be in [0, 1], got %g",
                  (double)slope);  // a NaN fails both comparisons
     return MAXK_OK;

@@ -52,6 +52,7 @@ __all__ = [
     "gat_edge_softmax_heads", "gat_edge_softmax_heads_backward", "heads_softmax_route",
     "gat_attention_heads", "gat_edge_alpha_heads", "heads_attention_route",
     "gat_attention_heads_backward", "heads_attention_backward_route", "edge_dropout_heads",
+    "dot_attention_heads", "dot_edge_alpha_heads",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -750,6 +751,73 @@ def gat_edge_alpha_heads(indptr: torch.Tensor, indices: torch.Tensor, s_dst: tor
     shape = (H, num_rows, num_cols, E)
     _launch_ws(dev, "maxk_gat_edge_alpha_heads", "maxk_gat_edge_alpha_heads_workspace_size", shape,
                (_ptr(indptr), _ptr(indices), _ptr(s_dst), _ptr(s_src), float(negative_slope),
+                _ptr(row_max), _ptr(row_sum), _ptr(out), *shape))
+    return out
+
+
+def _dot_operands(indptr, indices, q, cbsr_val, cbsr_idx, D, scale, validate):
+    """The operand checks of the two dot-product attention calls; returns (H, num_rows, num_cols,
+    k, scale as a float)."""
+    _need(q, "q", torch.float32)
+    if q.dim() != 3 or not 1 <= q.shape[0] <= MAX_HEADS or q.shape[2] != D:
+        raise RuntimeError(f"q must be [H, num_rows, dim_origin] with 1 <= H <= {MAX_HEADS}")
+    num_rows, num_cols, k = _heads_operands(indptr, indices, cbsr_val, cbsr_idx, None, validate, D)
+    if q.shape[1] != num_rows:
+        raise RuntimeError("q must be [H, num_rows, dim_origin]")
+    scale = float(scale)
+    if not (0.0 < scale < float("inf")):
+        raise RuntimeError(f"scale must be finite and > 0, got {scale}")
+    return q.shape[0], num_rows, num_cols, k, scale
+
+
+def dot_attention_heads(indptr: torch.Tensor, indices: torch.Tensor, q: torch.Tensor,
+                        cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor, dim_origin: int,
+                        scale: float, chunk: int = 0, validate: Optional[bool] = None,
+                        out: Optional[torch.Tensor] = None):
+    """(out [H, num_rows, D], row_max [H, num_rows], row_sum [H, num_rows]): scaled dot-product
+    attention of H heads on CBSR keys in one walk of the graph (maxk_dot_attention_heads).  The
+    logit of edge (r <- c) is scale * sum_l cbsr_val[c, l] * q[h, r, cbsr_idx[c, l]], q
+    [H, num_rows, D] the query of every destination mapped into the feature space; its softmax
+    over the row weighs the CBSR rows summed into out -- what edge_weight_grad_heads(grad_output=q),
+    the scale, H edge_softmax calls and spgemm_forward_heads compute, without logits or
+    coefficients [H, E] ever being stored.  row_max and row_sum are the softmax statistics of
+    every row and head; dot_edge_alpha_heads rebuilds the coefficients from them.
+    1 <= H <= MAX_HEADS; scale finite and > 0; bitwise repeatable."""
+    D = int(dim_origin)
+    H, num_rows, num_cols, k, scale = _dot_operands(indptr, indices, q, cbsr_val, cbsr_idx, D,
+                                                    scale, validate)
+    dev = cbsr_val.device
+    out = _heads_out(out, (H, num_rows, D), dev, "[H, num_rows, dim_origin]")
+    row_max = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
+    row_sum = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
+    shape = (num_rows, num_cols, indices.numel(), D, k, H, chunk)
+    _launch_ws(dev, "maxk_dot_attention_heads", "maxk_dot_attention_heads_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(q), scale, _ptr(cbsr_val), _ptr(cbsr_idx),
+                _ptr(out), _ptr(row_max), _ptr(row_sum), *shape))
+    return out, row_max, row_sum
+
+
+def dot_edge_alpha_heads(indptr: torch.Tensor, indices: torch.Tensor, q: torch.Tensor,
+                         cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor, dim_origin: int,
+                         scale: float, row_max: torch.Tensor, row_sum: torch.Tensor,
+                         chunk: int = 0, out: Optional[torch.Tensor] = None,
+                         validate: Optional[bool] = None) -> torch.Tensor:
+    """w[H, E] float32: the attention coefficients from the query, the CBSR and the row statistics
+    of dot_attention_heads, exp(logit - row_max) / row_sum per edge (maxk_dot_edge_alpha_heads):
+    one record gather per edge for all heads, no reductions over edges."""
+    D = int(dim_origin)
+    H, num_rows, num_cols, k, scale = _dot_operands(indptr, indices, q, cbsr_val, cbsr_idx, D,
+                                                    scale, validate)
+    _need(row_max, "row_max", torch.float32)
+    _need(row_sum, "row_sum", torch.float32)
+    if tuple(row_max.shape) != (H, num_rows) or tuple(row_sum.shape) != (H, num_rows):
+        raise RuntimeError("row_max and row_sum must be [H, num_rows]")
+    dev = cbsr_val.device
+    E = indices.numel()
+    out = _heads_out(out, (H, E), dev, "[H, num_e]")
+    shape = (num_rows, num_cols, E, D, k, H, chunk)
+    _launch_ws(dev, "maxk_dot_edge_alpha_heads", "maxk_dot_edge_alpha_heads_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(q), scale, _ptr(cbsr_val), _ptr(cbsr_idx),
                 _ptr(row_max), _ptr(row_sum), _ptr(out), *shape))
     return out
 

@@ -40,7 +40,8 @@ import torch.nn as nn
 from torch.autograd import Function
 
 import maxk_cuda_kernels as mk
-from maxk_spgemm_function import (maxk_edge_dropout_heads, maxk_gat_attention_heads, maxk_spgemm,
+from maxk_spgemm_function import (maxk_dot_attention_heads, maxk_dot_scores_heads,
+                                  maxk_edge_dropout_heads, maxk_gat_attention_heads, maxk_spgemm,
                                   maxk_spgemm_heads)
 
 
@@ -114,6 +115,15 @@ class CSRGraph:
         return maxk_gat_attention_heads(self.indptr, self.indices, s_dst, s_src, topk_values,
                                         topk_indices, dim, negative_slope, backward, dropout,
                                         seed)
+
+    def dot_attend_heads(self, topk_values, topk_indices, dim: int, q, scale: float):
+        """[H, V, dim]: scaled dot-product attention of H heads on the CBSR keys, from the
+        queries q [H, V, dim] mapped into the feature space, with the score and the softmax
+        inside the aggregation walk (maxk_dot_attention_heads): what maxk_dot_scores_heads, the
+        edge softmax per head and aggregate_heads give, without logits or alpha [H, E] stored;
+        alpha is a transient of the backward."""
+        return maxk_dot_attention_heads(self.indptr, self.indices, q, topk_values, topk_indices,
+                                        dim, scale)
 
 
 class MaxK(Function):
@@ -606,6 +616,82 @@ class MaxKMultiHeadGATConv(nn.Module):
             alpha = maxk_edge_dropout_heads(alpha, p, seed)
             agg = graph.aggregate_heads(topk_values, topk_indices, self.in_feats, alpha)
         rst = torch.bmm(agg, W.transpose(1, 2)).transpose(0, 1)          # [V, H, out]
+        if self.bias is not None:
+            rst = rst + self.bias
+        if self.activation is not None:
+            rst = self.activation(rst)
+        return rst
+
+
+class MaxKTransformerConv(nn.Module):
+    """Scaled dot-product (graph transformer) attention with num_heads heads on MaxK features;
+    returns [V, num_heads, out_feats]:
+    rst[v, h] = sum_{u in N(v)} alpha_hvu W_v,h x_sparse[u] + b_h,
+    alpha_hv. = softmax_u((W_q,h x_sparse[v]) . (W_k,h x_sparse[u]) / sqrt(out_feats)),
+    W_*,h = fc_*.weight[h * out_feats:(h + 1) * out_feats].  The MaxK trick serves the keys as
+    well as the values: (W_q x_v) . (W_k x_u) = q[h, v] . x_u with q[h] = (x_sparse W_q,h^T) W_k,h
+    in the feature space [H, V, in], and x_u is the CBSR row -- so the score of an edge is a dot
+    product of q with the packed record the aggregation gathers anyway.  As in
+    MaxKMultiHeadGATConv the aggregation runs on the CBSR, agg [H, V, in], and W_v follows it as
+    one bmm.  Gradients reach fc_q and fc_k through q (torch ops), fc_v, x_sparse through q and
+    topk_values through the scores and the aggregation.
+
+    attention="stored" (the default) computes the logits [H, E] (maxk_dot_scores_heads), their
+    softmax per head and the aggregation over the stored coefficients; attention="fused" runs
+    CSRGraph.dot_attend_heads, which keeps the row statistics [H, V] instead and rebuilds alpha
+    as a transient in the backward.  MAXK_DOT_ATTN=fused|stored overrides the argument.
+
+    attn_drop: dropout of alpha after the softmax's normalisation, in training mode, under the
+    mask of (seed, head, edge) (mk.edge_dropout_heads); forward(..., attn_seed=) fixes the seed.
+    The stored path only: the fused walk has no dropout yet and raises a ValueError."""
+
+    def __init__(self, in_feats: int, out_feats: int, num_heads: int, bias: bool = True,
+                 activation=None, attention: str = "stored", attn_drop: float = 0.0):
+        super().__init__()
+        self.attn_drop = _check_attn_drop(attn_drop)
+        if attention not in ("stored", "fused"):
+            raise ValueError(f'attention must be "stored" or "fused", got {attention!r}')
+        self.attention = attention
+        if not 1 <= int(num_heads) <= mk.MAX_HEADS:
+            raise ValueError(f"num_heads must be in [1, {mk.MAX_HEADS}], got {num_heads}")
+        self.in_feats, self.out_feats, self.num_heads = in_feats, out_feats, int(num_heads)
+        self.scale = float(out_feats) ** -0.5
+        self.fc_q = nn.Linear(in_feats, self.num_heads * out_feats, bias=False)
+        self.fc_k = nn.Linear(in_feats, self.num_heads * out_feats, bias=False)
+        self.fc_v = nn.Linear(in_feats, self.num_heads * out_feats, bias=False)
+        self.bias = nn.Parameter(torch.zeros(self.num_heads, out_feats)) if bias else None
+        self.activation = activation
+        gain = nn.init.calculate_gain("relu")  # as the GAT layers: Xavier-normal, ReLU gain
+        for fc in (self.fc_q, self.fc_k, self.fc_v):
+            nn.init.xavier_normal_(fc.weight, gain=gain)
+
+    def attention_mode(self) -> str:
+        """"fused" or "stored": MAXK_DOT_ATTN when it names one, else the `attention`
+        argument."""
+        forced = os.environ.get("MAXK_DOT_ATTN", "")
+        return forced if forced in ("fused", "stored") else self.attention
+
+    def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices,
+                attn_seed: Optional[int] = None):
+        H, O, I = self.num_heads, self.out_feats, self.in_feats
+        p = self.attn_drop if self.training else 0.0
+        fused = self.attention_mode() == "fused"
+        if fused and p > 0:
+            raise ValueError("MaxKTransformerConv: the fused walk has no dropout yet; use "
+                             'attention="stored" with attn_drop > 0')
+        Wq, Wk, Wv = (fc.weight.view(H, O, I) for fc in (self.fc_q, self.fc_k, self.fc_v))
+        # (W_q x_v) . (W_k x_u) = ((x_v W_q^T) W_k) . x_u: the query in the feature space
+        q = torch.matmul(torch.matmul(x_sparse, Wq.transpose(1, 2)), Wk)  # [H, V, in]
+        if fused:
+            agg = graph.dot_attend_heads(topk_values, topk_indices, I, q, self.scale)
+        else:
+            logits = maxk_dot_scores_heads(graph.indptr, graph.indices, q, topk_values,
+                                           topk_indices, self.scale)
+            alpha = torch.stack([edge_softmax(graph, logits[h]) for h in range(H)])
+            if p > 0:
+                alpha = maxk_edge_dropout_heads(alpha, p, attn_seed_of(attn_seed))
+            agg = graph.aggregate_heads(topk_values, topk_indices, I, alpha)
+        rst = torch.bmm(agg, Wv.transpose(1, 2)).transpose(0, 1)          # [V, H, out]
         if self.bias is not None:
             rst = rst + self.bias
         if self.activation is not None:

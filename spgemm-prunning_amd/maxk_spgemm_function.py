@@ -523,6 +523,125 @@ def maxk_gat_attention_heads(graph_indptr, graph_indices, s_dst, s_src, topk_val
                                                negative_slope, backward, dropout, seed)[0]
 
 
+def _dot_inputs(graph_indptr, graph_indices, q, topk_values, topk_indices):
+    """The operands of the dot-product attention functions as the kernels take them."""
+    sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
+    return (_i32(graph_indptr), _i32(graph_indices), _f32_act(q), _f32_act(topk_values),
+            sel.contiguous())
+
+
+def _f32_grad(g):
+    g = g.contiguous()
+    return g if g.dtype == torch.float32 else g.float()
+
+
+class MaxKDotScoresHeadsFunction(Function):
+    """The scaled dot-product scores of H heads on CBSR keys, stored:
+    apply(graph_indptr, graph_indices, q [H, V, D], topk_values [V, k], topk_indices [V, k],
+    scale) -> logits [H, E], logits[h, e] = scale * q[h, row(e)] . scatter(topk)[col(e)].
+
+    A composition of existing kernels, because the score of an edge is the aggregation's
+    edge-weight gradient with the query in the place of grad_out: the forward is
+    edge_weight_grad_heads(grad_output=q), the gradient of q is spgemm_forward_heads with the
+    logits' gradient as the edge weights, and the gradient of topk_values is
+    sspmm_backward_heads(values=grad, grad_output=q)."""
+
+    @staticmethod
+    def forward(ctx, graph_indptr, graph_indices, q, topk_values, topk_indices, scale):
+        _require_kernels()
+        indptr, indices, qf, vals, sel = _dot_inputs(graph_indptr, graph_indices, q, topk_values,
+                                                     topk_indices)
+        ctx.scale = float(scale)
+        ctx.q_dtype = q.dtype
+        logits = maxk_cuda_kernels.edge_weight_grad_heads(indptr, indices, vals, sel, qf)
+        ctx.save_for_backward(indptr, indices, qf, vals, sel)
+        return logits.mul_(ctx.scale)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        indptr, indices, qf, vals, sel = ctx.saved_tensors
+        g = _f32_grad(grad_output)
+        grad_q = grad_tv = None
+        if ctx.needs_input_grad[2]:
+            grad_q = maxk_cuda_kernels.spgemm_forward_heads(indptr, indices, g, vals, sel,
+                                                            qf.shape[2]).mul_(ctx.scale)
+            grad_q = grad_q.to(ctx.q_dtype)
+        if ctx.needs_input_grad[3]:
+            grad_tv = maxk_cuda_kernels.sspmm_backward_heads(indptr, indices, g, qf,
+                                                             sel).mul_(ctx.scale)
+        return None, None, grad_q, grad_tv, None, None
+
+
+def maxk_dot_scores_heads(graph_indptr, graph_indices, q, topk_values, topk_indices, scale):
+    """logits [H, E] = scale * q[h, row] . scatter(topk)[col] for the H heads of one CSR graph;
+    gradients for q and topk_values (MaxKDotScoresHeadsFunction)."""
+    _require_kernels()
+    return MaxKDotScoresHeadsFunction.apply(graph_indptr, graph_indices, q, topk_values,
+                                            topk_indices, scale)
+
+
+class MaxKDotAttentionHeadsFunction(Function):
+    """Scaled dot-product attention of H heads on CBSR keys with the score and the softmax inside
+    the aggregation walk: apply(graph_indptr, graph_indices, q [H, V, D], topk_values [V, k],
+    topk_indices [V, k], dim_origin, scale) -> (out [H, V, dim_origin], row_max, row_sum).
+
+    The forward is one maxk_cuda_kernels.dot_attention_heads call.  It saves the graph, q, the
+    CBSR and the two row statistics [H, V] -- no tensor of H * E elements.  The backward rebuilds
+    the coefficients with dot_edge_alpha_heads as a transient and runs the stored path's passes
+    on them: edge_weight_grad_heads for the coefficients' gradient, edge_softmax_backward per head
+    for the logits', spgemm_forward_heads on those for q, and for topk_values the sum of the
+    aggregation's feature gradient (sspmm_backward_heads on the coefficients) and the scores'
+    (sspmm_backward_heads on the logits' gradient against q)."""
+
+    @staticmethod
+    def forward(ctx, graph_indptr, graph_indices, q, topk_values, topk_indices, dim_origin, scale):
+        _require_kernels()
+        indptr, indices, qf, vals, sel = _dot_inputs(graph_indptr, graph_indices, q, topk_values,
+                                                     topk_indices)
+        ctx.scale = float(scale)
+        ctx.q_dtype = q.dtype
+        out, row_max, row_sum = maxk_cuda_kernels.dot_attention_heads(
+            indptr, indices, qf, vals, sel, int(dim_origin), ctx.scale)
+        ctx.save_for_backward(indptr, indices, qf, vals, sel, row_max, row_sum)
+        ctx.mark_non_differentiable(row_max, row_sum)
+        return out, row_max, row_sum
+
+    @staticmethod
+    def backward(ctx, grad_output, _grad_max, _grad_sum):
+        indptr, indices, qf, vals, sel, row_max, row_sum = ctx.saved_tensors
+        mk = maxk_cuda_kernels
+        g = _f32_grad(grad_output)
+        H, _, D = qf.shape
+        alpha = mk.dot_edge_alpha_heads(indptr, indices, qf, vals, sel, D, ctx.scale, row_max,
+                                        row_sum)
+        grad_a = mk.edge_weight_grad_heads(indptr, indices, vals, sel, g)
+        grad_l = torch.empty_like(grad_a)
+        for h in range(H):
+            mk.edge_softmax_backward(indptr, alpha[h], grad_a[h], out=grad_l[h])
+        del grad_a
+        grad_q = grad_tv = None
+        if ctx.needs_input_grad[2]:
+            grad_q = mk.spgemm_forward_heads(indptr, indices, grad_l, vals, sel, D)
+            grad_q = grad_q.mul_(ctx.scale).to(ctx.q_dtype)
+        if ctx.needs_input_grad[3]:
+            grad_tv = mk.sspmm_backward_heads(indptr, indices, alpha, g, sel)
+            grad_tv.add_(mk.sspmm_backward_heads(indptr, indices, grad_l, qf, sel),
+                         alpha=ctx.scale)
+        del alpha, grad_l
+        return None, None, grad_q, grad_tv, None, None, None
+
+
+def maxk_dot_attention_heads(graph_indptr, graph_indices, q, topk_values, topk_indices,
+                             dim_origin, scale):
+    """[H, V, dim_origin] = sum over a row's edges of softmax(scale * q[h, row] .
+    scatter(topk)[col]) * scatter(topk)[col], for the H heads of one CSR graph, without logits or
+    coefficients [H, E] being stored; gradients for q and topk_values
+    (MaxKDotAttentionHeadsFunction)."""
+    _require_kernels()
+    return MaxKDotAttentionHeadsFunction.apply(graph_indptr, graph_indices, q, topk_values,
+                                               topk_indices, dim_origin, scale)[0]
+
+
 class MaxKSpmmWrapper:
     """Holds the warp4 metadata of one graph (maxk_spgemm_function.py:214-267)."""
 

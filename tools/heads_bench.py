@@ -47,6 +47,15 @@ within every iteration so all of them see the same clocks and cache state:
                         stored path with torch.nn.functional.dropout on alpha, what a user would
                         write without the mask entries; the peak memory of one step of each
 
+  dot_attention_fwd_fused   mk.dot_attention_heads       one call, no logits, no alpha
+                                                                        (--pairs dot_attention)
+  dot_attention_fwd_stored  exactly what it replaces: mk.edge_weight_grad_heads(grad_output=q),
+                        the scale, H x mk.edge_softmax, then mk.spgemm_forward_heads
+  dot_alpha_fused / dot_alpha_stored   mk.dot_edge_alpha_heads from the statistics against the
+                        logits and the H softmaxes: what the fused backward pays to rebuild alpha
+  step_fused / step_stored     MaxKTransformerConv forward plus backward, attention="fused"
+                        against "stored", out_feats = D / H, with the peak memory of one step
+
 It reports the medians, the ratio heads / calls of each pair, and the run-to-run spread of the
 single-head baselines in this run, (max - min) / median over the iterations: the heads kernel
 counts as faster only where 1 - ratio exceeds that spread.  For the feature gradient it also
@@ -58,6 +67,8 @@ timed.  Writes one JSON file and prints it.
   python tools/heads_bench.py --pairs softmax,layer --heads 1,2,4,8 --out FILE
   python tools/heads_bench.py --pairs attention --heads 1,2,4,8 --out FILE
   python tools/heads_bench.py --pairs attention_dropout --heads 1,2,4,8 --out FILE
+  python tools/heads_bench.py --pairs dot_attention --graphs reddit:16,reddit:32,products:16,products:32
+                              --heads 1,2,4,8 --out FILE
 """
 import argparse
 import json
@@ -643,6 +654,112 @@ def run_attention_dropout(name, k, D, H, iters, warmup, seed, dev, slope=0.2, p=
     return r
 
 
+def run_dot_attention(name, k, D, H, iters, warmup, seed, dev):
+    """mk.dot_attention_heads against the scores, the H softmaxes and the forward it replaces,
+    mk.dot_edge_alpha_heads against the scores and softmaxes it replaces in the backward, and
+    MaxKTransformerConv's training step under attention="fused" against "stored", alternating
+    inside every iteration; the peak memory of one step of each."""
+    import maxk_layers as ML
+    V = bench.maxk_graph.PRESETS[name]["V"]
+    row_ptr, col = _graph(name, seed, dev)
+    E = col.numel()
+    gen = torch.Generator(device=dev).manual_seed(655)
+    q = torch.randn(H, V, D, generator=gen, device=dev)
+    cv, ci = mk.topk_cbsr(torch.rand(V, D, generator=gen, device=dev), k)
+    scale = float(D // H) ** -0.5
+    y_f, y_s = torch.empty(H, V, D, device=dev), torch.empty(H, V, D, device=dev)
+    lg = torch.empty(H, E, device=dev)
+    w = torch.empty(H, E, device=dev)
+    w2 = torch.empty(H, E, device=dev)
+    stats = []
+
+    def scores_and_softmax():
+        mk.edge_weight_grad_heads(row_ptr, col, cv, ci, q, out=lg, validate=False)
+        lg.mul_(scale)
+        for h in range(H):
+            mk.edge_softmax(row_ptr, lg[h], out=w[h], validate=False)
+
+    def fwd_fused():
+        stats[:] = mk.dot_attention_heads(row_ptr, col, q, cv, ci, D, scale, out=y_f,
+                                          validate=False)[1:]
+
+    def fwd_stored():
+        scores_and_softmax()
+        mk.spgemm_forward_heads(row_ptr, col, w, cv, ci, D, out=y_s, validate=False)
+
+    def alpha_fused():
+        mk.dot_edge_alpha_heads(row_ptr, col, q, cv, ci, D, scale, stats[0], stats[1], out=w2,
+                                validate=False)
+
+    ops = (("dot_attention_fwd_fused", fwd_fused), ("dot_attention_fwd_stored", fwd_stored),
+           ("dot_alpha_fused", alpha_fused), ("dot_alpha_stored", scores_and_softmax))
+    mk.dot_attention_heads(row_ptr, col, q, cv, ci, D, scale, out=y_f, validate=True)
+    for _ in range(warmup):
+        for _, fn in ops:
+            fn()
+    torch.cuda.synchronize()
+    ts = {n: [] for n, _ in ops}
+    for _ in range(iters):
+        for n, fn in ops:
+            ts[n].append(timed(fn))
+    s = {n: summary(t) for n, t in ts.items()}
+    r = dict(kind="dot_attention", graph=name, V=V, E=E, D=D, k=k, H=H, scale=scale, **s)
+    r["out_max_diff_over_max"] = float((y_f - y_s).abs().max() / y_s.abs().max())
+    r["alpha_max_abs_diff"] = float((w2 - w).abs().max())
+    r["workspace_bytes_fused"] = int(mk._lib().maxk_dot_attention_heads_workspace_size(
+        V, V, E, D, k, H, 0))
+    r["alpha_bytes"] = 4 * H * E
+    del y_f, y_s, w, w2, lg, q
+    stats.clear()
+    torch.cuda.empty_cache()
+
+    graph = ML.CSRGraph(row_ptr, col)
+    torch.manual_seed(7)
+    conv = ML.MaxKTransformerConv(D, D // H, H).to(dev)
+    xs, vals, idx = ML.maxk(torch.rand(V, D, device=dev), k)
+    xs = xs.detach().requires_grad_(True)
+    vals = vals.detach().requires_grad_(True)
+    mk.transpose_plan(col, V)
+
+    def step(mode):
+        conv.attention = mode
+        conv.zero_grad(set_to_none=True)
+        xs.grad = vals.grad = None
+        conv(graph, xs, vals, idx).sum().backward()
+
+    modes = ("fused", "stored")
+    saved = os.environ.pop("MAXK_DOT_ATTN", None)
+    try:
+        for _ in range(warmup):
+            for mode in modes:
+                step(mode)
+        torch.cuda.synchronize()
+        tl = {mode: [] for mode in modes}
+        for _ in range(iters):
+            for mode in modes:
+                tl[mode].append(timed(lambda: step(mode)))
+        for mode in modes:  # the peak of one step, the other mode's buffers released
+            conv.zero_grad(set_to_none=True)
+            xs.grad = vals.grad = None
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            step(mode)
+            torch.cuda.synchronize()
+            r[f"step_{mode}_peak_bytes"] = int(torch.cuda.max_memory_allocated())
+            r[f"step_{mode}_peak_over_resident_bytes"] = int(torch.cuda.max_memory_allocated()
+                                                             - base)
+    finally:
+        if saved is not None:
+            os.environ["MAXK_DOT_ATTN"] = saved
+    sl = {f"step_{mode}": summary(t) for mode, t in tl.items()}
+    r.update(sl)
+    s.update(sl)
+    _fused_ratios(r, s, ("dot_attention_fwd", "dot_alpha", "step"))
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--graphs", default="reddit:16,products:32")
@@ -677,6 +794,9 @@ def main():
             if "attention_dropout" in asked:
                 rs.append(run_attention_dropout(name, int(k), args.dim, H, args.iters,
                                                 args.warmup, args.seed, dev))
+            if "dot_attention" in asked:
+                rs.append(run_dot_attention(name, int(k), args.dim, H, args.iters, args.warmup,
+                                            args.seed, dev))
             if "layer" in asked and H >= 2:
                 rs.append(run_layer(name, int(k), args.dim, H, args.iters, args.warmup,
                                     args.seed, dev))
