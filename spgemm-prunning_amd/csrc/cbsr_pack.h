@@ -1,6 +1,6 @@
 // Packed CBSR records and the token-stream item size, shared by the kernels that gather one
 // record per edge: the forward (spgemm_fwd.hip), the edge-weight gradient (edge_grad.hip) and
-// the multi-head forward (spgemm_fwd_heads.hip).
+// the multi-head forwards and the GAT backward (through heads_walk.h).
 // Each translation unit gets its own copy of the pack kernels (anonymous namespace, like
 // slab_fixup_kernel in common.h).
 #pragma once

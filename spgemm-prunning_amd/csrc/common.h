@@ -314,8 +314,23 @@ inline int lanes_per_edge(int k) {
     return g;
 }
 
+// The longest item of a walk that addresses a piece's 4-B elements through one descriptor with
+// 32-bit offsets.
+constexpr int kMaxChunk = 1 << 24;
+
 // ---- device helpers ----
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));  // what the non-temporal builtins take
+
+// x, the same in every lane, as a wave-uniform value (an SGPR).
+__device__ __forceinline__ float uniform(float x) {
+    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x)));
+}
+
+// The value subtracted from a softmax piece's logits: its max, or 0 for a piece of nothing but
+// -inf.
+__device__ __forceinline__ float shift_of(float m) { return m == -__builtin_inff() ? 0.f : m; }
 
 // Zero n 4-byte words on the stream with a kernel.  Launch paths use this instead of
 // hipMemsetAsync: a memset captured into a hipGraph (ROCm 7.2) zeroed its buffer on the first
@@ -344,6 +359,21 @@ inline int64_t xcd_grid(int64_t blocks) { return (blocks + kXcds - 1) / kXcds * 
 __device__ __forceinline__ int xcd_contiguous_block(int b, int grid) {
     const int per = grid / kXcds;
     return (b % kXcds) * per + b / kXcds;
+}
+// One wave per item, kWavesPerBlock items per workgroup, in XCD-contiguous order (MAXK_FWD_XCD):
+// the grid, and the item of the calling wave (the grid's last waves have none: an item at or
+// past n_items, -1 from item_of_wave, and the whole wave returns).
+inline dim3 item_grid(int n_items) {
+    const int64_t blocks = ceil_div(n_items, kWavesPerBlock);
+    return dim3((unsigned)(MAXK_FWD_XCD ? xcd_grid(blocks) : blocks));
+}
+__device__ __forceinline__ int wave_item() {
+    const int blk = MAXK_FWD_XCD ? xcd_contiguous_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    return blk * kWavesPerBlock + (int)(threadIdx.x / kWave);
+}
+__device__ __forceinline__ int item_of_wave(int n_items) {
+    const int item = wave_item();
+    return item < n_items ? item : -1;
 }
 // The same inside windows of kXcds * run blocks (grid a multiple of kXcds): each XCD walks
 // runs of `run` consecutive blocks, one run per window, so work whose cost varies along the

@@ -8,11 +8,12 @@
 // what maxk_edge_weight_grad_heads (grad_out := q), the scale, H edge softmaxes and
 // maxk_spgemm_forward_heads compute, without logits or alpha [H, E] ever existing.  The score and
 // the aggregation read the same packed record of column c, so the walk gathers it for both.  The
-// pieces are those of gat_attention_heads.hip (records packed once, token-stream items, one
-// wavefront per item under CutHubRows, KG lanes per group, G = 64 / KG LDS copies of the output
-// row, the heads in passes of HC, the fix-up of the cut rows) and of edge_grad.hip (the H rows
-// q[h, r, :] of the piece staged side by side in LDS, one fma per slot and a fixed butterfly per
-// logit):
+// walk is the hub-row heads walk of heads_walk.h, shared with spgemm_fwd_heads.hip and
+// gat_attention_heads.hip (records packed once, token-stream items, one wavefront per item under
+// CutHubRows, KG lanes per group, G = 64 / KG LDS copies of the output row, the heads in passes
+// of HC, the fix-up of the cut rows; its rules are stated there); the logit is edge_grad.hip's
+// (the H rows q[h, r, :] of the piece staged side by side in LDS, one fma per slot and a fixed
+// butterfly per logit):
 //
 //  1. launch_cbsr_pack fills the workspace's records.
 //  2. dath_fwd_kernel, per row piece: the H query rows are staged as scale * q (one rounding per
@@ -30,8 +31,7 @@
 //     * a row inside one item is stored as acc / z with (m, z); a hub row's pieces are stored
 //       unnormalised, the owner's into out and the statistics, a continuation's into the item's
 //       slab [H, n_items, D] and slab statistics [H, n_items].
-//  3. dath_fixup_kernel merges a hub row's pieces in item order: m = max m_i, each piece scaled by
-//     exp(m_i - m), one division by z = sum z_i exp(m_i - m).
+//  3. softmax_fixup_kernel (heads_walk.h) merges a hub row's pieces in item order.
 // A row whose z is not a positive number (a NaN or +Inf logit: z is NaN; only -Inf logits: z = 0)
 // is NaN wherever it has an addend and exactly 0 elsewhere: such rows are walked once more with
 // the weight NaN and stored undivided.  A row without edges stores zeros in out and both
@@ -44,18 +44,13 @@
 // LDS per wave: (H + G) * DS floats (16.6 KB at H = 8, G = 8, D = 256; 12.5 KB at k = 16).
 #include <cmath>
 
-#include "cbsr_pack.h"
 #include "edge_softmax.h"
+#include "heads_walk.h"
 
 namespace maxk {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kMaxH = MAXK_MAX_HEADS;
-
-__device__ __forceinline__ float uniform(float x) {
-    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x)));
-}
 
 // ---- the logit, shared by both sweeps of the forward and by the alpha walk ----------------------
 // One slot of an edge's dot product against the staged (scaled) query row qh: an idle lane's
@@ -225,69 +220,10 @@ __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
                     ps += p[u];
                 }
             }
-            for (int lb = 0; lb < k; lb += KG) {
-                const int sl = lb + l0;
-                const bool lok = sl < k;
-                const uint32_t lc = (uint32_t)(lok ? sl : k - 1);
-                const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
-                float v[U];
-                int s[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const bool live = lok && active && base + u * EP + eg < n;
-                    float *a = &acc_g[live ? min(s[u], trash) : trash];
-                    *a = __builtin_fmaf(p[u], v[u], *a);
-                }
-            }
+            scatter_records<KG, U>(acc_g, rrs, RS, k, trash, l0, c, p, active, base, EP, eg, n);
         }
     }
     return ps;
-}
-
-// dst[0:D] = (acc[0:D] + acc[stride + 0:D] + ... over nc copies) / div; the copies read are
-// zeroed.  One wave.
-__device__ __forceinline__ void flush_head(float *acc, int nc, int stride, float *__restrict__ dst,
-                                           int D, float div, bool scale, bool vec, bool nt,
-                                           int lane) {
-    if (vec) {
-        for (int j = lane * 4; j < D; j += kWave * 4) {
-            float4 a = *reinterpret_cast<float4 *>(&acc[j]);
-            *reinterpret_cast<float4 *>(&acc[j]) = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int g = 1; g < nc; ++g) {
-                float4 *pg = reinterpret_cast<float4 *>(&acc[g * stride + j]);
-                const float4 b = *pg;
-                a.x += b.x;
-                a.y += b.y;
-                a.z += b.z;
-                a.w += b.w;
-                *pg = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            if (scale) {
-                a.x = a.x / div;
-                a.y = a.y / div;
-                a.z = a.z / div;
-                a.w = a.w / div;
-            }
-            if (nt)  // output rows streamed past the caches (the record lines stay)
-                __builtin_nontemporal_store(__builtin_bit_cast(f32x4, a),
-                                            reinterpret_cast<f32x4 *>(&dst[j]));
-            else
-                *reinterpret_cast<float4 *>(&dst[j]) = a;
-        }
-    } else {
-        for (int j = lane; j < D; j += kWave) {
-            float a = acc[j];
-            acc[j] = 0.f;
-            for (int g = 1; g < nc; ++g) {
-                a += acc[g * stride + j];
-                acc[g * stride + j] = 0.f;
-            }
-            if (scale) a = a / div;
-            dst[j] = a;
-        }
-    }
 }
 
 template <int KG, int U>
@@ -298,32 +234,27 @@ __global__ __launch_bounds__(kBlock) void dath_fwd_kernel(
     float *__restrict__ slab, float *__restrict__ slab_m, float *__restrict__ slab_z,
     int32_t *__restrict__ slab_row, int num_rows, int64_t num_e, int D, int DS, int k, int chunk,
     int n_items, int H, int HC, int flags) {
-    // flags: bit 0 16-B row stores (D % 4 == 0, out 16-B aligned), bit 1 non-temporal out rows,
-    // bit 2 16-B query loads (D % 4 == 0, q 16-B aligned)
-    constexpr int G = kWave / KG;  // lane groups = LDS copies per wave
+    // flags: store_flags (heads_walk.h), and bit 2 16-B query loads (D % 4 == 0, q 16-B aligned)
+    constexpr int G = kWave / KG;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int wid = threadIdx.x / kWave;
     const int lane = lane_id();
-    const int blk = MAXK_FWD_XCD ? xcd_contiguous_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-    const int item = blk * kWavesPerBlock + wid;
+    const int item = wave_item();
     if (item >= n_items) return;  // whole wave; no workgroup barrier below
-    float *qrow = lds + (size_t)wid * (H + G) * DS;
+    float *qrow = lds + (size_t)(threadIdx.x / kWave) * (H + G) * DS;
     float *acc = qrow + H * DS;
-    for (int j = lane * 4; j < (H + G) * DS; j += kWave * 4)
-        *reinterpret_cast<float4 *>(&qrow[j]) = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int grp = lane / KG;
-    float *acc_g = acc + grp * DS;
-    const int EP = G / HC;  // edges per wave step (HC <= G)
-    const int eg = grp / HC, hh = grp % HC;
-    const bool grp_ok = grp < EP * HC;
+    zero_wave_lds(qrow, (H + G) * DS, lane);
+    const PassGeom<KG> g(lane, HC, acc, DS);
     const bool vec = flags & 1, nt = flags & 2, qvec = flags & 4;
 
-    // Edges [sb, se) of row r into dst rows of stride hstride per head, the statistics into
-    // st_m / st_z [h * st_stride].  whole: the piece is the row, stored normalised; else it is
-    // a hub row's piece, stored as it is.  Every head is stored, an empty piece as zeros.
-    auto row_heads = [&](int r, int64_t sb, int64_t se, float *__restrict__ dst, int64_t hstride,
-                         float *__restrict__ st_m, float *__restrict__ st_z, int64_t st_stride,
-                         bool whole, bool to_out) {
+    // Edges [sb, se) of row r: an owned row's into out and the row statistics, a continuation's
+    // into the item's slab and slab statistics.  Every head is stored, an empty piece as zeros.
+    walk_hub_item(row_ptr, slab_row, num_rows, num_e, item, chunk, lane,
+                  [&](int r, int64_t sb, int64_t se, bool whole, bool to_out) {
+        float *__restrict__ dst = to_out ? out + (int64_t)r * D : slab + (int64_t)item * D;
+        const int64_t hstride = (int64_t)(to_out ? num_rows : n_items) * D;
+        float *__restrict__ st_m = to_out ? row_max + r : slab_m + item;
+        float *__restrict__ st_z = to_out ? row_sum + r : slab_z + item;
+        const int64_t st_stride = to_out ? num_rows : n_items;
         const int n = (int)(se - sb);
         float m[kMaxH];
 #pragma unroll
@@ -335,8 +266,8 @@ __global__ __launch_bounds__(kBlock) void dath_fwd_kernel(
             piece_max<KG, U>(qrow, col_idx + sb, rec, RS, n, H, DS, k, DS - 1, lane, m);
         }
         for (int h0 = 0; h0 < H; h0 += HC) {
-            const int head = h0 + hh;
-            const bool active = grp_ok && head < H;
+            const int head = h0 + g.hh;
+            const bool active = g.grp_ok && head < H;
             float mh = -INFINITY;
 #pragma unroll
             for (int h = 0; h < kMaxH; ++h)
@@ -345,28 +276,20 @@ __global__ __launch_bounds__(kBlock) void dath_fwd_kernel(
             float ps = 0.f;
             wave_lds_fence();
             if (n > 0)
-                ps = walk_dot<KG, U, false>(acc_g, qh, col_idx, shift_of(mh), rec, RS, (int)sb,
-                                            (int)se, k, DS - 1, EP, eg, active, lane);
-            // z of head h0 + j: its EP groups' sums in group order
-            auto z_of = [&](int j) {
-                float z = 0.f;
-                for (int e = 0; e < EP; ++e) z += __shfl(ps, (e * HC + j) * KG);
-                return uniform(z);
-            };
-            int bad = 0;
-            for (int j = 0; j < HC && h0 + j < H; ++j)
-                if (!(z_of(j) > 0.f)) bad |= 1 << j;
+                ps = walk_dot<KG, U, false>(g.acc_g, qh, col_idx, shift_of(mh), rec, RS, (int)sb,
+                                            (int)se, k, DS - 1, g.EP, g.eg, active, lane);
+            const int bad = bad_heads<KG>(ps, g.EP, HC, h0, H);
             if (whole && n > 0 && bad) {  // rare: NaN wherever such a head's row has an addend
                 wave_lds_fence();
-                walk_dot<KG, U, true>(acc_g, qh, col_idx, 0.f, rec, RS, (int)sb, (int)se, k,
-                                      DS - 1, EP, eg, active && ((bad >> hh) & 1), lane);
+                walk_dot<KG, U, true>(g.acc_g, qh, col_idx, 0.f, rec, RS, (int)sb, (int)se, k,
+                                      DS - 1, g.EP, g.eg, active && ((bad >> g.hh) & 1), lane);
             }
             wave_lds_fence();
             for (int j = 0; j < HC && h0 + j < H; ++j) {
-                const float zj = z_of(j);
+                const float zj = pass_z<KG>(ps, j, g.EP, HC);
                 const bool ok = !((bad >> j) & 1);
-                flush_head(acc + j * DS, EP, HC * DS, dst + (int64_t)(h0 + j) * hstride, D, zj,
-                           whole && ok, vec, nt && to_out, lane);
+                flush_head<false>(acc + j * DS, g.EP, HC * DS, dst + (int64_t)(h0 + j) * hstride,
+                                  D, zj, whole && ok, vec, nt && to_out, lane, 1.f);
                 // the head's maximum sits in the lanes of group j (edge slot 0, head h0 + j)
                 const float mj = uniform(__shfl(mh, j * KG));
                 if (lane == 0) {
@@ -376,91 +299,7 @@ __global__ __launch_bounds__(kBlock) void dath_fwd_kernel(
             }
         }
         wave_lds_fence();
-    };
-
-    const ItemRange it = item_range(row_ptr, num_rows, num_e, item, chunk);
-    int r = it.r;
-
-    // Continuation of row r - 1 (its token precedes d0): only a hub row leaves one, and a slab
-    // per head for the fixup.
-    int cont = -1;
-    if (r > 0) {
-        const RowPiece p =
-            cont_piece(CutHubRows{}, it.p_lo, it.d1, r, row_ptr[r - 1], row_ptr[r], chunk);
-        if (p.sb < p.se && p.hub) {
-            row_heads(r - 1, p.sb, p.se, slab + (int64_t)item * D, (int64_t)n_items * D,
-                      slab_m + item, slab_z + item, n_items, false, false);
-            cont = r - 1;
-        }
-    }
-    if (lane == 0) slab_row[item] = cont;
-
-    // Rows whose token lies in [d0, d1): this item owns them.
-    while (r < num_rows) {
-        const int64_t rb = row_ptr[r];
-        if (!row_owned(it.d1, r, rb)) break;
-        const RowPiece p = row_piece(CutHubRows{}, it.d1, r, rb, row_ptr[r + 1], chunk);
-        row_heads(r, rb, p.se, out + (int64_t)r * D, (int64_t)num_rows * D, row_max + r,
-                  row_sum + r, num_rows, !p.hub, true);
-        ++r;
-    }
-}
-
-// The merge of a hub row's pieces, one head per blockIdx.y, 16 lanes per item, as
-// gat_attention_heads.hip's gath_fixup_kernel: the thread group of the first item holding a slab
-// of the row merges the owner's piece (in out and the statistics) and the row's slabs in item
-// order.  Every hub row has a slab: it is longer than an item.
-__global__ __launch_bounds__(kBlock) void dath_fixup_kernel(
-    const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
-    const uint8_t *__restrict__ rec, int RS, int k, const float *__restrict__ slab_all,
-    const float *__restrict__ slab_m_all, const float *__restrict__ slab_z_all,
-    const int32_t *__restrict__ slab_row, float *__restrict__ out_all,
-    float *__restrict__ row_max_all, float *__restrict__ row_sum_all, int64_t num_rows, int D,
-    int n_items) {
-    const int item = (int)((blockIdx.x * (int64_t)kBlock + threadIdx.x) / 16);
-    const int g = threadIdx.x % 16;
-    if (item >= n_items) return;
-    const int row = slab_row[item];
-    if (row < 0 || (item > 0 && slab_row[item - 1] == row)) return;
-    const int64_t h = blockIdx.y;
-    const float *sm = slab_m_all + h * n_items + item;
-    const float *sz = slab_z_all + h * n_items + item;
-    const float *sl = slab_all + (h * n_items + item) * D;
-    float *o = out_all + (h * num_rows + row) * D;
-    float *rm = row_max_all + h * num_rows + row;
-    float *rs = row_sum_all + h * num_rows + row;
-    int n = 1;
-    while (item + n < n_items && slab_row[item + n] == row) ++n;
-    const float m0 = *rm, z0 = *rs;
-    float m = m0;
-    for (int i = 0; i < n; ++i) m = fmaxf(m, sm[i]);
-    // a piece of nothing but -inf has sum 0 (or NaN) and scale exp(-inf) = 0
-    const float shift = shift_of(m);
-    const float c0 = expf(m0 - shift);
-    float z = z0 * c0;
-    for (int i = 0; i < n; ++i) z += sz[i] * expf(sm[i] - shift);
-    if (z > 0.f) {
-        for (int j = g; j < D; j += 16) {
-            float a = o[j] * c0;
-            for (int i = 0; i < n; ++i) a += sl[(int64_t)i * D + j] * expf(sm[i] - shift);
-            o[j] = a / z;
-        }
-    } else {  // rare: NaN wherever the row has an addend, 0 elsewhere
-        for (int j = g; j < D; j += 16) o[j] = 0.f;
-        __threadfence();  // the zeros land before the NaNs of other lanes (one wave, in order)
-        const int64_t rb = row_ptr[row], re = row_ptr[row + 1];
-        for (int64_t e = rb; e < re; ++e) {
-            const uint8_t *p = rec + (int64_t)col_idx[e] * RS + 4 * k;
-            for (int l = g; l < k; l += 16) {
-                const int s = reinterpret_cast<const uint16_t *>(p)[l];
-                if (s < D) o[s] = NAN;  // a folded or out-of-range selector is >= 0x100
-            }
-        }
-    }
-    if (g == 0) {
-        *rm = m;
-        *rs = z;
-    }
+    });
 }
 
 // ---- w[h, e] = exp(l_he - row_max[h, r]) / row_sum[h, r] ----------------------------------------
@@ -567,64 +406,42 @@ __global__ __launch_bounds__(kBlock) void dath_alpha_kernel(
     }
 }
 
-// A piece is addressed through a descriptor of 4 * n bytes with 32-bit offsets.
-constexpr int kDotMaxChunk = 1 << 24;
 // Waves per SIMD the kernels' VGPRs allow (the kernel-resource-usage remarks).
 constexpr int kDotFwdWaves = 4;
 constexpr int kDotAlphaWaves = 6;
 
+// The items are sized for the waves a CU holds (walk_chunk): by VGPRs, fewer when the H query
+// rows and G accumulator copies per wave fill the CU's LDS first (8 waves at H = 8, k <= 8,
+// D = 256).
 struct DotLayout {
-    int chunk, n_items, RS, DS, kg, hc;
-    bool wide;
-    size_t lds, slab_off, m_off, z_off, row_off, total;
+    int chunk, n_items, hc;
+    size_t lds, total;  // lds: per workgroup
+    RecordGeom R;
+    SlabLayout S;
 };
-
-// What both entries share: the records, the lane groups and whether the table is addressable.
-DotLayout dot_records(int64_t num_cols, int D, int k) {
-    DotLayout L{};
-    L.RS = record_stride(k, num_cols);
-    L.DS = copy_stride(D);
-    const int g = lanes_per_edge(k);
-    L.kg = g < 8 ? 8 : g;
-    L.wide = !(num_cols < (1 << 24) && (uint64_t)num_cols * (uint64_t)L.RS < (1ull << 32));
-    return L;
-}
-
-// The items are sized for the waves a CU holds: by VGPRs, fewer when the H query rows and G
-// accumulator copies per wave fill the CU's LDS first (8 waves at H = 8, k <= 8, D = 256).
-int dot_chunk(int64_t num_rows, int64_t num_e, int chunk, size_t lds_per_block, int waves) {
-    const int by_lds = (int)(kPullLdsBytes / lds_per_block) * kWavesPerBlock;
-    const int by_regs = waves * 4;
-    int c = fwd_chunk(num_rows, num_e, chunk, by_lds < by_regs ? by_lds : by_regs);
-    return c > kDotMaxChunk ? kDotMaxChunk : c;
-}
 
 DotLayout dot_fwd_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, int k, int H,
                          int chunk) {
-    DotLayout L = dot_records(num_cols, D, k);
-    const int G = kWave / L.kg;
-    const int np = (H + G - 1) / G;
-    L.hc = (H + np - 1) / np;
-    L.lds = (size_t)kWavesPerBlock * (H + G) * L.DS * sizeof(float);
-    L.chunk = dot_chunk(num_rows, num_e, chunk, L.lds, kDotFwdWaves);
+    DotLayout L{};
+    L.R = record_geom(num_cols, D, k);
+    L.hc = heads_per_pass(H, L.R.kg);
+    L.lds = (size_t)kWavesPerBlock * (H + kWave / L.R.kg) * L.R.DS * sizeof(float);
+    L.chunk = walk_chunk(num_rows, num_e, chunk, L.lds, kDotFwdWaves * 4);
     L.n_items = token_items(num_rows, num_e, L.chunk);
-    const int64_t cap = item_cap(num_rows + num_e, chunk, L.n_items);
-    const size_t stat = al256((size_t)cap * H * sizeof(float));
-    L.slab_off = al256((size_t)num_cols * L.RS);
-    L.m_off = L.slab_off + al256((size_t)cap * H * D * sizeof(float));
-    L.z_off = L.m_off + stat;
-    L.row_off = L.z_off + stat;
-    L.total = L.row_off + al256((size_t)cap * sizeof(int32_t));
+    L.S = slab_layout(item_cap(num_rows + num_e, chunk, L.n_items), H, D,
+                      al256((size_t)num_cols * L.R.RS), true);
+    L.total = L.S.end;
     return L;
 }
 
 DotLayout dot_alpha_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, int k, int H,
                            int chunk) {
-    DotLayout L = dot_records(num_cols, D, k);
-    L.lds = (size_t)kWavesPerBlock * (H * L.DS + kWave + 2 * kMaxH) * sizeof(float);
-    L.chunk = dot_chunk(num_rows, num_e, chunk, L.lds, kDotAlphaWaves);
+    DotLayout L{};
+    L.R = record_geom(num_cols, D, k);
+    L.lds = (size_t)kWavesPerBlock * (H * L.R.DS + kWave + 2 * kMaxH) * sizeof(float);
+    L.chunk = walk_chunk(num_rows, num_e, chunk, L.lds, kDotAlphaWaves * 4);
     L.n_items = token_items(num_rows, num_e, L.chunk);
-    L.total = al256((size_t)num_cols * L.RS);
+    L.total = al256((size_t)num_cols * L.R.RS);
     if (L.total == 0) L.total = 256;  // never empty: one query serves any num_cols
     return L;
 }
@@ -643,12 +460,7 @@ int check_dot(int64_t num_rows, int64_t num_cols, int64_t num_e, float scale, in
     if (int rc = check_sizes(num_rows, num_cols, num_e, chunk_edges)) return rc;
     MAXK_REQUIRE(std::isfinite(scale) && scale > 0.f, "scale must be finite and > 0, got %g",
                  (double)scale);
-    MAXK_REQUIRE(dim_origin >= 1 && dim_origin <= kMaxDim, "dim_origin must be in [1,256], got %d",
-                 dim_origin);
-    MAXK_REQUIRE(dim_k >= 1 && dim_k <= dim_origin, "dim_k must be in [1,dim_origin], got %d",
-                 dim_k);
-    MAXK_REQUIRE(num_cols * (int64_t)dim_k < (1LL << 31), "num_cols*k too large");
-    return MAXK_OK;
+    return check_cbsr_dims(dim_origin, dim_k, num_cols);
 }
 
 }  // namespace
@@ -682,18 +494,15 @@ extern "C" int maxk_dot_attention_heads(const int32_t *row_ptr, const int32_t *c
                  "row_ptr / out / row_max / row_sum must not be NULL");
     const int D = dim_origin, k = dim_k, H = num_heads;
     hipStream_t s = as_stream(stream);
-    if (num_e == 0) {  // nothing to walk: zero rows and statistics
-        if (int rc = zero_words(out, (int64_t)H * num_rows * D, s)) return rc;
-        if (int rc = zero_words(row_max, (int64_t)H * num_rows, s)) return rc;
-        return zero_words(row_sum, (int64_t)H * num_rows, s);
-    }
+    if (num_e == 0) return zero_heads_out(out, row_max, row_sum, H, num_rows, D, s);
     MAXK_REQUIRE(col_idx && q && cbsr_val && cbsr_idx,
                  "col_idx / q / cbsr_val / cbsr_idx must not be NULL");
     MAXK_REQUIRE(num_cols > 0, "edges present but num_cols == 0");
     const DotLayout L = dot_fwd_layout(num_rows, num_cols, num_e, D, k, H, chunk_edges);
-    MAXK_REQUIRE(!L.wide, "num_cols: the fused dot-product attention takes tables below 2^24 "
+    const RecordGeom &R = L.R;
+    MAXK_REQUIRE(!R.wide, "num_cols: the fused dot-product attention takes tables below 2^24 "
                  "columns and 4 GiB of records (%lld columns of %d bytes)", (long long)num_cols,
-                 L.RS);
+                 R.RS);
     if (int rc = check_workspace(workspace, workspace_bytes, L.total)) return rc;
     MAXK_REQUIRE(((uintptr_t)cbsr_val & 3) == 0 && ((uintptr_t)q & 3) == 0 &&
                      ((uintptr_t)out & 3) == 0 && ((uintptr_t)row_max & 3) == 0 &&
@@ -701,32 +510,27 @@ extern "C" int maxk_dot_attention_heads(const int32_t *row_ptr, const int32_t *c
                  "float buffers must be 4-B aligned");
     char *ws = reinterpret_cast<char *>(workspace);
     uint8_t *rec = reinterpret_cast<uint8_t *>(ws);
-    float *slab = reinterpret_cast<float *>(ws + L.slab_off);
-    float *slab_m = reinterpret_cast<float *>(ws + L.m_off);
-    float *slab_z = reinterpret_cast<float *>(ws + L.z_off);
-    int32_t *slab_row = reinterpret_cast<int32_t *>(ws + L.row_off);
-    if (int rc = launch_cbsr_pack(cbsr_val, cbsr_idx, rec, num_cols, k, L.RS, D, L.DS - 1, s))
+    float *slab = reinterpret_cast<float *>(ws + L.S.slab_off);
+    float *slab_m = reinterpret_cast<float *>(ws + L.S.m_off);
+    float *slab_z = reinterpret_cast<float *>(ws + L.S.z_off);
+    int32_t *slab_row = reinterpret_cast<int32_t *>(ws + L.S.row_off);
+    if (int rc = launch_cbsr_pack(cbsr_val, cbsr_idx, rec, num_cols, k, R.RS, D, R.DS - 1, s))
         return rc;
     constexpr int U = MAXK_FWD_U;
-    const bool big = (double)H * num_rows * D * 4 > (double)kInfinityCacheBytes;
-    const int flags = (D % 4 == 0 && ((uintptr_t)out & 15) == 0 ? 1 : 0) |
-                      ((MAXK_FWD_OUT_NT == 1 || (MAXK_FWD_OUT_NT == 2 && big)) ? 2 : 0) |
-                      (D % 4 == 0 && ((uintptr_t)q & 15) == 0 ? 4 : 0);
-    const bool ok = with_const<8, 16, 32, 64>(L.kg, [&](auto kg_c) {
+    const int flags =
+        store_flags(out, H, num_rows, D) | (D % 4 == 0 && ((uintptr_t)q & 15) == 0 ? 4 : 0);
+    const bool ok = with_const<8, 16, 32, 64>(R.kg, [&](auto kg_c) {
         constexpr int KG = decltype(kg_c)::value;
         hipLaunchKernelGGL((dath_fwd_kernel<KG, U>), item_grid(L.n_items), dim3(kBlock), L.lds, s,
-                           row_ptr, col_idx, q, scale, rec, L.RS, out, row_max, row_sum, slab,
-                           slab_m, slab_z, slab_row, (int)num_rows, num_e, D, L.DS, k, L.chunk,
+                           row_ptr, col_idx, q, scale, rec, R.RS, out, row_max, row_sum, slab,
+                           slab_m, slab_z, slab_row, (int)num_rows, num_e, D, R.DS, k, L.chunk,
                            L.n_items, H, L.hc, flags);
     });
-    if (!ok) return bad_lanes(L.kg);
+    if (!ok) return bad_lanes(R.kg);
     MAXK_LAUNCHED("dath_fwd_kernel");
-    hipLaunchKernelGGL(dath_fixup_kernel,
-                       dim3((unsigned)ceil_div(L.n_items, kBlock / 16), (unsigned)H), dim3(kBlock),
-                       0, s, row_ptr, col_idx, rec, L.RS, k, slab, slab_m, slab_z, slab_row, out,
-                       row_max, row_sum, num_rows, D, L.n_items);
-    MAXK_LAUNCHED("dath_fixup_kernel");
-    return MAXK_OK;
+    return launch_softmax_fixup<false>(row_ptr, col_idx, rec, R.RS, k, slab, slab_m, slab_z,
+                                       slab_row, out, row_max, row_sum, num_rows, D, L.n_items, H,
+                                       1.f, s);
 }
 
 extern "C" size_t maxk_dot_edge_alpha_heads_workspace_size(int64_t num_rows, int64_t num_cols,
@@ -757,8 +561,9 @@ extern "C" int maxk_dot_edge_alpha_heads(const int32_t *row_ptr, const int32_t *
                  "be NULL");
     const int D = dim_origin, k = dim_k, H = num_heads;
     const DotLayout L = dot_alpha_layout(num_rows, num_cols, num_e, D, k, H, chunk_edges);
-    MAXK_REQUIRE(!L.wide, "num_cols: the dot-product alpha takes tables below 2^24 columns and "
-                 "4 GiB of records (%lld columns of %d bytes)", (long long)num_cols, L.RS);
+    const RecordGeom &R = L.R;
+    MAXK_REQUIRE(!R.wide, "num_cols: the dot-product alpha takes tables below 2^24 columns and "
+                 "4 GiB of records (%lld columns of %d bytes)", (long long)num_cols, R.RS);
     if (int rc = check_workspace(workspace, workspace_bytes, L.total)) return rc;
     MAXK_REQUIRE(((uintptr_t)cbsr_val & 3) == 0 && ((uintptr_t)q & 3) == 0 &&
                      ((uintptr_t)row_max & 3) == 0 && ((uintptr_t)row_sum & 3) == 0 &&
@@ -766,17 +571,17 @@ extern "C" int maxk_dot_edge_alpha_heads(const int32_t *row_ptr, const int32_t *
                  "float buffers must be 4-B aligned");
     hipStream_t s = as_stream(stream);
     uint8_t *rec = reinterpret_cast<uint8_t *>(workspace);
-    if (int rc = launch_cbsr_pack(cbsr_val, cbsr_idx, rec, num_cols, k, L.RS, D, L.DS - 1, s))
+    if (int rc = launch_cbsr_pack(cbsr_val, cbsr_idx, rec, num_cols, k, R.RS, D, R.DS - 1, s))
         return rc;
     constexpr int U = MAXK_FWD_U;
     const int qvec = D % 4 == 0 && ((uintptr_t)q & 15) == 0;
-    const bool ok = with_const<8, 16, 32, 64>(L.kg, [&](auto kg_c) {
+    const bool ok = with_const<8, 16, 32, 64>(R.kg, [&](auto kg_c) {
         constexpr int KG = decltype(kg_c)::value;
         hipLaunchKernelGGL((dath_alpha_kernel<KG, U>), item_grid(L.n_items), dim3(kBlock), L.lds,
-                           s, row_ptr, col_idx, rec, L.RS, q, scale, row_max, row_sum, w,
-                           (int)num_rows, num_e, D, L.DS, k, L.chunk, L.n_items, H, qvec);
+                           s, row_ptr, col_idx, rec, R.RS, q, scale, row_max, row_sum, w,
+                           (int)num_rows, num_e, D, R.DS, k, L.chunk, L.n_items, H, qvec);
     });
-    if (!ok) return bad_lanes(L.kg);
+    if (!ok) return bad_lanes(R.kg);
     MAXK_LAUNCHED("dath_alpha_kernel");
     return MAXK_OK;
 }

@@ -32,8 +32,7 @@
 //       5.06 against 5.00 ms products-sized at k = 32, the latter inside the run-to-run
 //       spread: MAXK_EGRAD_LDS_STORE=0, profiles/r07/edge_grad/.)
 // No atomics, no allocation, copy or synchronisation: the launch can be captured.
-#include "cbsr_pack.h"
-#include "common.h"
+#include "heads_walk.h"  // the host side's record geometry and item size
 
 #ifndef MAXK_EGRAD_U  // edge-gradient: wave steps of record loads in flight
 #define MAXK_EGRAD_U 8
@@ -334,25 +333,17 @@ __global__ __launch_bounds__(kBlock) void edge_grad_heads_kernel(
 // Waves one CU holds at once: 8 per SIMD by VGPRs (at most 64, the kernel-resource-usage
 // remarks); the LDS row per wave (about 1 KB) is far from the CU's 160 KB.
 constexpr int kEdgeGradResident = 32;
-// An item's pieces are addressed through descriptors of 4 * n bytes with 32-bit offsets.
-constexpr int kEdgeGradMaxChunk = 1 << 24;
 
-struct EdgeGradLayout {
-    int chunk, n_items, RS, DS, kg;
-    bool wide;
+struct EdgeGradLayout : RecordGeom {
+    int chunk, n_items;
     size_t total;
 };
 
 EdgeGradLayout edge_grad_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, int k,
                                 int chunk) {
-    EdgeGradLayout L{};
-    L.RS = record_stride(k, num_cols);
-    L.DS = copy_stride(D);
-    const int g = lanes_per_edge(k);
-    L.kg = g < 8 ? 8 : g;
-    L.wide = !(num_cols < (1 << 24) && (uint64_t)num_cols * (uint64_t)L.RS < (1ull << 32));
+    EdgeGradLayout L{record_geom(num_cols, D, k)};
     L.chunk = fwd_chunk(num_rows, num_e, chunk, kEdgeGradResident);
-    if (L.chunk > kEdgeGradMaxChunk) L.chunk = kEdgeGradMaxChunk;
+    if (L.chunk > kMaxChunk) L.chunk = kMaxChunk;
     L.n_items = token_items(num_rows, num_e, L.chunk);
     L.total = al256((size_t)num_cols * L.RS);
     return L;
@@ -439,10 +430,7 @@ EdgeGradLayout edge_grad_heads_layout(int64_t num_rows, int64_t num_cols, int64_
                                       int k, int H, int chunk) {
     EdgeGradLayout L = edge_grad_layout(num_rows, num_cols, num_e, D, k, chunk);
     const size_t per_block = (size_t)kWavesPerBlock * (H * L.DS + kWave) * sizeof(float);
-    const int by_lds = (int)(kPullLdsBytes / per_block) * kWavesPerBlock;
-    L.chunk = fwd_chunk(num_rows, num_e, chunk,
-                        by_lds < kEdgeGradHeadsResident ? by_lds : kEdgeGradHeadsResident);
-    if (L.chunk > kEdgeGradMaxChunk) L.chunk = kEdgeGradMaxChunk;
+    L.chunk = walk_chunk(num_rows, num_e, chunk, per_block, kEdgeGradHeadsResident);
     L.n_items = token_items(num_rows, num_e, L.chunk);
     return L;
 }

@@ -16,7 +16,6 @@ constexpr int kLR = 8;               // lanes per short row
 constexpr int kNG = kWave / kLR;     // short rows per wave round
 constexpr int kPer = 4;              // edges per lane of a short row
 constexpr int kShort = kLR * kPer;   // a row of at most this many edges is a short row
-constexpr int kMaxChunk = 1 << 24;   // pieces are walked with 32-bit offsets of 4-B elements
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float x) {
@@ -47,9 +46,6 @@ __device__ __forceinline__ float lane_tree(float x) {
     return x;
 }
 
-// The value subtracted from a piece's logits: its max, or 0 for a piece of nothing but -inf.
-__device__ __forceinline__ float shift_of(float m) { return m == -INFINITY ? 0.f : m; }
-
 // The logit of an edge of one row: pointers are offset to the piece, i is 32-bit.
 template <bool GAT>
 struct Logits {
@@ -76,12 +72,6 @@ struct Slots {
     float *__restrict__ a;
     float *__restrict__ b;
 };
-
-__device__ __forceinline__ int item_of_wave(int n_items) {
-    const int blk = MAXK_FWD_XCD ? xcd_contiguous_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-    const int item = blk * kWavesPerBlock + (int)(threadIdx.x / kWave);
-    return item < n_items ? item : -1;
-}
 
 // ---- whole-wave pieces (n edges, n >= 1, wave-uniform) --------------------------------------
 
@@ -569,10 +559,6 @@ inline SlotLayout slot_layout(int64_t n, int64_t num_e, int chunk, size_t base) 
     L.b_off = L.a_off + bytes;
     L.end = L.b_off + bytes;
     return L;
-}
-dim3 item_grid(int n_items) {
-    const int64_t blocks = ceil_div(n_items, kWavesPerBlock);
-    return dim3((unsigned)(MAXK_FWD_XCD ? xcd_grid(blocks) : blocks));
 }
 inline dim3 slot_grid(int n_items) { return dim3((unsigned)ceil_div(2 * (int64_t)n_items, kBlock)); }
 

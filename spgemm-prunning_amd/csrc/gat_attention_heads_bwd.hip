@@ -49,8 +49,8 @@
 #include <cmath>
 
 #include "attn_dropout.h"
-#include "cbsr_pack.h"
 #include "edge_softmax.h"
+#include "heads_walk.h"  // the host side's record geometry
 #include "sspmm_bwd.h"
 
 // Wave steps of record loads in flight.  4: 97 to 122 VGPRs over the twelve instantiations (four
@@ -384,9 +384,8 @@ constexpr int kBwdResident = 16;
 
 // Workspace: [T (num_e + 1 rows) and the phase-2 slabs | records | ss_t | gzT | row slots x H |
 // column slots x H].
-struct BwdLayout {
-    int chunk, n_items, RS, DS, kg, hp;
-    bool wide;
+struct BwdLayout : RecordGeom {
+    int chunk, n_items, hp;
     size_t rec_off, ss_off, gz_off, srow_off, sa_off, total;
     int64_t sstride;  // floats between two heads' row slots
     SlotLayoutH cols;
@@ -394,13 +393,8 @@ struct BwdLayout {
 
 BwdLayout bwd_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, int k, int H,
                      int chunk) {
-    BwdLayout L{};
-    L.RS = record_stride(k, num_cols);
-    L.DS = copy_stride(D);
+    BwdLayout L{record_geom(num_cols, D, k)};
     L.hp = hp_of(H);
-    const int g = lanes_per_edge(k);
-    L.kg = g < 8 ? 8 : g;
-    L.wide = !(num_cols < (1 << 24) && (uint64_t)num_cols * (uint64_t)L.RS < (1ull << 32));
     const size_t per_block = (size_t)kWavesPerBlock * H * L.DS * sizeof(float);
     const int by_lds = (int)(kPullLdsBytes / per_block) * kWavesPerBlock;
     L.chunk = fwd_chunk(num_rows, num_e, chunk, by_lds < kBwdResident ? by_lds : kBwdResident);
@@ -490,11 +484,7 @@ int attention_heads_backward(
     if (int rc = check_heads(num_heads)) return rc;
     if (int rc = check_sizes(num_rows, num_cols, num_e, chunk_edges)) return rc;
     if (int rc = check_slope(negative_slope)) return rc;
-    MAXK_REQUIRE(dim_origin >= 1 && dim_origin <= kMaxDim, "dim_origin must be in [1,256], got %d",
-                 dim_origin);
-    MAXK_REQUIRE(dim_k >= 1 && dim_k <= dim_origin, "dim_k must be in [1,dim_origin], got %d",
-                 dim_k);
-    MAXK_REQUIRE(num_cols * (int64_t)dim_k < (1LL << 31), "num_cols*k too large");
+    if (int rc = check_cbsr_dims(dim_origin, dim_k, num_cols)) return rc;
     MAXK_REQUIRE((grad_s_dst || num_rows == 0) && ((grad_s_src && grad_cbsr) || num_cols == 0),
                  "grad_s_dst / grad_s_src / grad_cbsr must not be NULL");
     const int D = dim_origin, k = dim_k, H = num_heads;

@@ -129,8 +129,6 @@ __global__ __launch_bounds__(kPackBlock) void cbsr_records_kernel(const float *_
 // the next record loads keeps its bytes live through the batch's peak register use.  They are
 // non-temporal (the stream must not push the record lines out of L2), and the pending bytes sit
 // four to a register with the batch position kept wave-uniform.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 template <int KG, int U, bool WIDE, bool EMIT = false>
 struct EdgeWalker {
     static constexpr int G = kWave / KG;  // edges per wave step

@@ -17,8 +17,6 @@ namespace {
 
 enum { kAtomic = 0, kStore = 1, kStoreX4 = 2, kStoreX4W = 3, kStoreX4S = 4 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // A contribution row's 16 B in phase 2.  NT: rows of whole 128-B lines (k % 32 == 0) are read
 // once, so non-temporally -- ogbn-products-sized csc backward k = 32 7.85 -> 7.77 ms, with the
 // selector stream 6.71 -> 6.60, k = 64 15.14 -> 14.75; rows sharing a line (k <= 16) need

@@ -1,6 +1,6 @@
 """GPU: attention dropout under the stored-nowhere Philox mask -- mk.edge_dropout_heads
 (attn_dropout.hip), mk.gat_attention_heads(dropout=, seed=) (gath_fwd_kernel<.., true>,
-gath_fixup_kernel<true>), mk.gat_attention_heads_backward(dropout=, seed=)
+softmax_fixup_kernel<true> of heads_walk.h), mk.gat_attention_heads_backward(dropout=, seed=)
 (gath_bwd_kernel<.., true>), the autograd functions and the two GAT layers -- against
 tests/attn_dropout_ref.py (numpy Philox, float64, derived bounds).
 

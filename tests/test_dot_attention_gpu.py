@@ -6,8 +6,9 @@ tests/dot_attention_ref.py (float64, with its derived bounds), against the compo
 against dense float64 torch autograd.
 
 Which kernels.  Every non-empty forward launches cbsr_pack_kernel or cbsr_pack4_kernel
-(k % 4 == 0), dath_fwd_kernel<KG, 8> and dath_fixup_kernel; every non-empty alpha call the pack
-and dath_alpha_kernel<KG, 8>.  KG = 8 for k = 3, 7, 8, 16 for k = 16, 32 for k = 24, 32, 64 for
+(k % 4 == 0), dath_fwd_kernel<KG, 8> and softmax_fixup_kernel<false> (heads_walk.h, which also
+holds the walk the forward kernel shares with the other heads forwards); every non-empty alpha
+call the pack and dath_alpha_kernel<KG, 8>.  KG = 8 for k = 3, 7, 8, 16 for k = 16, 32 for k = 24, 32, 64 for
 k = 96 (k > KG: the several-slots-per-lane path of edge_logits and walk_dot).  The heads per pass
 are HC = ceil(H / ceil(H / G)), G = 64 / KG: at H = 1, 2, 3, 5, 8 that is 1, 2, 3, 5, 8 (KG = 8),
 1, 2, 3, 3, 4 (KG = 16), 1, 2, 2, 2, 2 (KG = 32) and 1 (KG = 64), so test_parity, which runs
@@ -15,7 +16,7 @@ every (k, H) of SHAPES x HEADS at the auto item size and at 64 tokens, reaches t
 dath_fwd_kernel instantiations with one and several passes, full and partly filled last passes
 and idle groups (H = 3 at G = 8).  test_alpha_from_the_statistics runs k = 16 and, by
 test_parity's shapes in test_alpha_shapes, every KG of dath_alpha_kernel.  The NaN pass of
-dath_fwd_kernel (walk_dot<.., true>) and of dath_fixup_kernel run in test_non_finite (rows inside
+dath_fwd_kernel (walk_dot<.., true>) and of softmax_fixup_kernel run in test_non_finite (rows inside
 an item and the hub row at chunk 64).
 
 The largest err / bound seen on an MI355X is in test_ratios_are_reported's output; the figures of

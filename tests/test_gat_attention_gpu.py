@@ -6,14 +6,15 @@ replaces (mk.gat_edge_softmax_heads then mk.spgemm_forward_heads) and against th
 autograd.
 
 Which kernels.  Every non-empty forward launches cbsr_pack_kernel or cbsr_pack4_kernel
-(k % 4 == 0), gath_interleave_kernel<HP>, gath_fwd_kernel<KG, HP, 8> and gath_fixup_kernel;
+(k % 4 == 0), gath_interleave_kernel<HP>, gath_fwd_kernel<KG, HP, 8> and softmax_fixup_kernel<false>
+(heads_walk.h, which also holds the walk the forward kernel shares with the other heads forwards);
 every non-empty alpha call gath_interleave_kernel<HP> and gath_alpha_kernel<HP>.  HP = 2, 2, 4, 8,
 8 for H = 1, 2, 3, 5, 8; KG = 8 for k = 3, 7, 8, 16 for k = 16, 32 for k = 24, 32, 64 for k = 96.
 test_parity runs every (k, H) of SHAPES x HEADS, so it reaches the twelve gath_fwd_kernel
 instantiations (KG in 8, 16, 32, 64 x HP in 2, 4, 8) and the three interleaves;
 test_alpha_from_the_statistics runs H in 1, 3, 8: the three gath_alpha_kernel instantiations.
 The others run KG = 16 with HP = 4 (H = 3) or HP = 8 (H = 8) unless their docstrings say
-otherwise.  The NaN pass of gath_fwd_kernel (walk_attn<.., true>) and of gath_fixup_kernel run
+otherwise.  The NaN pass of gath_fwd_kernel (walk_attn<.., true>) and of softmax_fixup_kernel run
 in test_non_finite (rows inside an item and the hub row at chunk 64).
 
 The largest err / bound seen on an MI355X is in test_ratios_are_reported's output; the figures

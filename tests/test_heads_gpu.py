@@ -1,6 +1,6 @@
-"""GPU: the multi-head aggregation -- maxk_spgemm_forward_heads (spgemm_fwd_heads.hip) and
-maxk_edge_weight_grad_heads (edge_grad.hip) through the binding, the autograd surface
-(maxk_spgemm_heads) and the layer (MaxKMultiHeadGATConv), against tests/heads_ref.py: the
+"""GPU: the multi-head aggregation -- maxk_spgemm_forward_heads (spgemm_fwd_heads.hip, on the walk
+of heads_walk.h) and maxk_edge_weight_grad_heads (edge_grad.hip) through the binding, the autograd
+surface (maxk_spgemm_heads) and the layer (MaxKMultiHeadGATConv), against tests/heads_ref.py: the
 oracle's forward and numpy float64 dot products per head, pinned to torch autograd by
 test_heads_cpu.py.  Bounds are numerics' own, (n + 8) * 2^-24 * sum|terms| with the 2^-149 floor
 for subnormal inputs.  Shapes are the module graphs of tests/numerics.py (S: hub rows of 590 and
