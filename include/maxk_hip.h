@@ -665,6 +665,80 @@ int maxk_dot_edge_alpha_heads(const int32_t *row_ptr, const int32_t *col_idx, co
                               void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Fused backward of maxk_dot_attention_heads: both gradients in one walk of the graph,
+ *   l_he     = scale * sum_l cbsr_val[c,l] * q[h, r, s]           e in row r, c = col_idx[e],
+ *   alpha_he = exp(l_he - row_max[h,r]) / row_sum[h,r]            s = cbsr_idx[c,l]
+ *                                                                (as maxk_dot_edge_alpha_heads)
+ *   ga_he    = sum_l cbsr_val[c,l] * grad_out[h, r, s]
+ *   t_hr     = sum_{j : out[h,r,j] != 0} out[h,r,j] * grad_out[h,r,j]
+ *   gl_he    = alpha_he * (ga_he - t_hr)
+ *   grad_q[h,r,j]  = scale * sum_{e in r} gl_he * x_c[j]          x_c the scattered CBSR row
+ *   grad_cbsr[c,l] = sum_h sum_{e -> c} (alpha_he * grad_out[h,r,s] + scale * gl_he * q[h,r,s])
+ * -- what maxk_dot_edge_alpha_heads, maxk_edge_weight_grad_heads, num_heads
+ * maxk_edge_softmax_backward calls, maxk_spgemm_forward_heads and two maxk_sspmm_backward_heads
+ * calls compute in six record gathers per edge, with no tensor of num_heads * num_e elements in
+ * an input, an output or the workspace beside the edge-major gl [num_e, HP] the aggregation of
+ * grad_q reads.  out, row_max and row_sum are what the forward returned; t, the softmax
+ * backward's sum over the row of alpha * ga, is the dot product of the two dense rows out[h,r,:]
+ * and grad_out[h,r,:], which every work item forms for itself, so a row cut over items is walked
+ * once.  The terms with out == 0 are skipped: the forward stores an exact 0 in every column no
+ * edge of the row selects, and a NaN or Inf of grad_out there reaches nothing (the rule of
+ * maxk_gat_attention_heads_backward).
+ * col_ptr / csc_eid: the graph's maxk_transpose_plan.  grad_q [num_heads, num_rows, dim_origin]
+ *   and grad_cbsr [num_cols, dim_k] (the heads summed per edge in head order, the edges in CSC
+ *   slot order).  The reference has no counterpart.
+ * Per edge the first walk loads col_idx once and one packed record (value and selector); the
+ *   logit is formed by the forward's device functions on the same staged row scale * q, so
+ *   exp(l - row_max) <= 1 as in the alpha entry; alpha and gl are computed once per edge and
+ *   head.  The second walk is the multi-head forward's with gl as the weights and a product by
+ *   scale at the end; a hub row's pieces are added in item order.  No global and no LDS atomics.
+ * Shapes: any 1 <= dim_k <= dim_origin <= 256 (dim_k % 4 != 0, odd dim_origin, dim_k > 64),
+ *   1 <= num_heads <= MAXK_MAX_HEADS, any value, one head included; num_rows != num_cols
+ *   allowed; num_e == 0 writes zeros to both outputs; a table past 2^24 columns or 4 GiB of
+ *   packed records is rejected with MAXK_ERR_INVALID.  scale: finite and > 0.
+ * Writes: every element of both outputs.  An element of a row without edges, a column of grad_q
+ *   that no neighbour of the row selects, a column of the table no edge reads and a slot whose
+ *   selector is >= dim_origin give an exact 0; a repeated selector's slots each receive the
+ *   column's gradient.
+ * Numerics (tests/dot_attention_bwd_ref.py): alpha within the forward's weight bound, ga within
+ *   the edge gradient's, t within (n_t + 8) u sum|out g| plus the error of `out` carried through
+ *   grad_out; gl the product bound of the three; the sums the sum bounds, with one more rounding
+ *   for the staged scale * q and one for the product by scale.  The one difference from the
+ *   stored path: there t is summed over the row's edges, here over its columns, so a row of a
+ *   single edge gives gl within the bound, not the exact 0 of ga - ga.
+ * Non-finite values follow the IEEE evaluation of the formulas: a NaN in q[h, r, j] at a column
+ *   a neighbour of r selects reaches head h's grad_q row r and grad_cbsr of the columns r reads,
+ *   at a column none selects it reaches nothing; a -Inf logit gives alpha = 0 and contributes 0
+ *   for a finite ga; a NaN of grad_out in a column the row does not select reaches nothing.
+ * Bitwise repeatable for equal arguments whatever the workspace held (every sum's order is
+ *   fixed by the graph, chunk_edges, dim_k and num_heads); head h's slice of grad_q does not
+ *   depend, bitwise, on the other heads' q, out, statistics or grad_out (grad_cbsr sums the
+ *   heads).
+ * Memory, as the top comment: the workspace (contribution rows T [num_e + 1, dim_k] and the
+ *   phase-2 slabs, the packed records, gl [num_e, HP] and the second walk's per-head slabs of the
+ *   cut rows -- one array of HP * num_e floats and never room for a second) is exactly the
+ *   queried size, 256-B aligned, and may hold anything; a shorter one is rejected ("workspace too
+ *   small") on the host before any launch; nothing is written outside the outputs and the
+ *   workspace, inputs are never written; no allocation, copy or synchronisation.  The size is
+ *   non-decreasing in num_e.
+ * Argument errors (num_heads outside [1, MAXK_MAX_HEADS], a null pointer, negative sizes, scale
+ *   not finite or <= 0, k / D range): MAXK_ERR_INVALID with a message naming the argument,
+ *   before any launch.
+ * chunk_edges: tokens per wavefront work item of every walk, 0 = each walk's auto rule.
+ * ------------------------------------------------------------------------- */
+size_t maxk_dot_attention_heads_backward_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                        int64_t num_e, int32_t dim_origin,
+                                                        int32_t dim_k, int32_t num_heads,
+                                                        int32_t chunk_edges);
+int maxk_dot_attention_heads_backward(
+    const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr, const int32_t *csc_eid,
+    const float *q, float scale, const float *cbsr_val, const uint8_t *cbsr_idx, const float *out,
+    const float *row_max, const float *row_sum, const float *grad_out, float *grad_q,
+    float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+    int32_t dim_k, int32_t num_heads, int32_t chunk_edges, void *workspace,
+    size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Backward outer-product sampled SpMM (SSpMM):
  *   grad_cbsr[c,l] = sum_{e=(r->c)} edge_val[e] * grad_out[r, cbsr_idx[c,l]] / row_div[r]
  *                  = (A^T diag(1/row_div) G)[c, cbsr_idx[c,l]]     (from the CSR of A)

@@ -44,73 +44,12 @@
 // LDS per wave: (H + G) * DS floats (16.6 KB at H = 8, G = 8, D = 256; 12.5 KB at k = 16).
 #include <cmath>
 
+#include "dot_logit.h"
 #include "edge_softmax.h"
 #include "heads_walk.h"
 
 namespace maxk {
 namespace {
-
-constexpr int kMaxH = MAXK_MAX_HEADS;
-
-// ---- the logit, shared by both sweeps of the forward and by the alpha walk ----------------------
-// One slot of an edge's dot product against the staged (scaled) query row qh: an idle lane's
-// clamped slot contributes nothing.
-__device__ __forceinline__ float logit_term(float v, int s, const float *qh, int trash, bool lok,
-                                            float acc) {
-    const float t = __builtin_fmaf(v, qh[min(s, trash)], acc);
-    return lok ? t : acc;
-}
-// The group's slots summed by the fixed butterfly of edge_grad.hip's group_sum: every lane of the
-// group holds the same bits.
-template <int KG>
-__device__ __forceinline__ float logit_sum(float acc) {
-    return lane_tree<KG, Sum>(acc);
-}
-// k > KG (k > 64): a lane takes its slots l0, l0 + KG, ... in l order, the record from the caches.
-template <int KG, int U>
-__device__ __forceinline__ void edge_logits(const __amdgpu_buffer_rsrc_t rrs, int RS,
-                                            const int (&c)[U], const float *qh, int k, int trash,
-                                            int l0, float (&l)[U]) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) l[u] = 0.f;
-    for (int lb = 0; lb < k; lb += KG) {
-        const int sl = lb + l0;
-        const bool lok = sl < k;
-        const uint32_t lc = (uint32_t)(lok ? sl : k - 1);
-        const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
-        float v[U];
-        int s[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
-#pragma unroll
-        for (int u = 0; u < U; ++u) l[u] = logit_term(v[u], s[u], qh, trash, lok, l[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) l[u] = logit_sum<KG>(l[u]);
-}
-
-// qrow[h * DS + j] = scale * q[h, row, j] for the H heads (the pad columns [D, DS) hold zeros and
-// are never staged over).  One wave.
-__device__ __forceinline__ void stage_query(float *qrow, const float *__restrict__ q, int64_t row,
-                                            int64_t num_rows, int H, int D, int DS, float scale,
-                                            bool vec, int lane) {
-    for (int h = 0; h < H; ++h) {
-        const float *g = q + ((int64_t)h * num_rows + row) * D;
-        float *d = qrow + h * DS;
-        if (vec) {
-            for (int j = lane * 4; j < D; j += kWave * 4) {
-                float4 x = *reinterpret_cast<const float4 *>(&g[j]);
-                x.x *= scale;
-                x.y *= scale;
-                x.z *= scale;
-                x.w *= scale;
-                *reinterpret_cast<float4 *>(&d[j]) = x;
-            }
-        } else {
-            for (int j = lane; j < D; j += kWave) d[j] = g[j] * scale;
-        }
-    }
-}
 
 // Sweep 1 over the edges [sb, sb + n) (n >= 1) of a piece whose query rows are staged: m[h] = the
 // piece's largest logit of head h (-inf for h >= H), wave-uniform.  One group per edge.
@@ -444,23 +383,6 @@ DotLayout dot_alpha_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, in
     L.total = al256((size_t)num_cols * L.R.RS);
     if (L.total == 0) L.total = 256;  // never empty: one query serves any num_cols
     return L;
-}
-
-bool dot_shape_ok(int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
-                  int32_t dim_k, int32_t num_heads, int32_t chunk_edges) {
-    return sizes_ok(num_rows, num_cols, num_e) && dim_origin >= 1 && dim_origin <= kMaxDim &&
-           dim_k >= 1 && dim_k <= dim_origin && chunk_edges >= 0 && num_heads >= 1 &&
-           num_heads <= MAXK_MAX_HEADS;
-}
-
-// The argument checks both entries share, in the order the header states them.
-int check_dot(int64_t num_rows, int64_t num_cols, int64_t num_e, float scale, int32_t dim_origin,
-              int32_t dim_k, int32_t num_heads, int32_t chunk_edges) {
-    if (int rc = check_heads(num_heads)) return rc;
-    if (int rc = check_sizes(num_rows, num_cols, num_e, chunk_edges)) return rc;
-    MAXK_REQUIRE(std::isfinite(scale) && scale > 0.f, "scale must be finite and > 0, got %g",
-                 (double)scale);
-    return check_cbsr_dims(dim_origin, dim_k, num_cols);
 }
 
 }  // namespace

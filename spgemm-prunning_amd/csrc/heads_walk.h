@@ -1,7 +1,8 @@
 // The hub-row heads walk, stated once for the three multi-head forwards that run it:
 // spgemm_fwd_heads.hip (weights from edge_val), gat_attention_heads.hip (the GAT softmax of
 // interleaved scores) and dot_attention_heads.hip (the softmax of dot-product logits).  Each of
-// them computes its own weights; everything around the weights is here.
+// them computes its own weights; everything around the weights is here.  The grad_q aggregation
+// of dot_attention_heads_bwd.hip runs it too, with the edge-major gl [E, HP] as the weights.
 //
 // One wavefront per item of the token stream (token_items.h) under the hub-row cut rule
 // (CutHubRows).  With KG = pow2ceil(k) lanes per group (>= 8, <= 64) a wave has G = 64 / KG lane

@@ -52,7 +52,8 @@ __all__ = [
     "gat_edge_softmax_heads", "gat_edge_softmax_heads_backward", "heads_softmax_route",
     "gat_attention_heads", "gat_edge_alpha_heads", "heads_attention_route",
     "gat_attention_heads_backward", "heads_attention_backward_route", "edge_dropout_heads",
-    "dot_attention_heads", "dot_edge_alpha_heads",
+    "dot_attention_heads", "dot_edge_alpha_heads", "dot_attention_heads_backward",
+    "dot_attention_backward_route",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -820,6 +821,72 @@ def dot_edge_alpha_heads(indptr: torch.Tensor, indices: torch.Tensor, q: torch.T
                (_ptr(indptr), _ptr(indices), _ptr(q), scale, _ptr(cbsr_val), _ptr(cbsr_idx),
                 _ptr(row_max), _ptr(row_sum), _ptr(out), *shape))
     return out
+
+
+def dot_attention_heads_backward(indptr: torch.Tensor, indices: torch.Tensor, q: torch.Tensor,
+                                 cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor,
+                                 out: torch.Tensor, row_max: torch.Tensor, row_sum: torch.Tensor,
+                                 grad_output: torch.Tensor, scale: float, chunk: int = 0,
+                                 validate: Optional[bool] = None, plan=None):
+    """(grad_q [H, num_rows, D], grad_cbsr [num_cols, k]) of dot_attention_heads from its three
+    results and the gradient of `out`, in one call (maxk_dot_attention_heads_backward): what
+    dot_edge_alpha_heads, edge_weight_grad_heads, H edge_softmax_backward calls,
+    spgemm_forward_heads and two sspmm_backward_heads calls compute, with no [H, E] tensor
+    allocated.  The row sum of the softmax backward is taken as the dot product of out[h, r] and
+    grad_output[h, r], so `out` must be the forward's.  Uses the graph's transpose plan (cached
+    per `indices`, or `plan=` from transpose_plan()).  Bitwise repeatable; the same operand
+    checks as dot_attention_heads."""
+    _need(grad_output, "grad_output", torch.float32)
+    _need(out, "out", torch.float32)
+    _need(q, "q", torch.float32)
+    if q.dim() != 3:
+        raise RuntimeError(f"q must be [H, num_rows, dim_origin] with 1 <= H <= {MAX_HEADS}")
+    D = q.shape[2]
+    H, num_rows, num_cols, k, scale = _dot_operands(indptr, indices, q, cbsr_val, cbsr_idx, D,
+                                                    scale, validate)
+    if tuple(grad_output.shape) != (H, num_rows, D) or tuple(out.shape) != (H, num_rows, D):
+        raise RuntimeError("out and grad_output must be [H, num_rows, dim_origin]")
+    _need(row_max, "row_max", torch.float32)
+    _need(row_sum, "row_sum", torch.float32)
+    if tuple(row_max.shape) != (H, num_rows) or tuple(row_sum.shape) != (H, num_rows):
+        raise RuntimeError("row_max and row_sum must be [H, num_rows]")
+    dev = cbsr_val.device
+    col_ptr, csc_eid = plan if plan is not None else transpose_plan(indices, num_cols)
+    grad_q = torch.empty(H, num_rows, D, dtype=torch.float32, device=dev)
+    grad_cbsr = torch.empty(num_cols, k, dtype=torch.float32, device=dev)
+    shape = (num_rows, num_cols, indices.numel(), D, k, H, chunk)
+    _launch_ws(dev, "maxk_dot_attention_heads_backward",
+               "maxk_dot_attention_heads_backward_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(q), scale,
+                _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), _ptr(row_max), _ptr(row_sum),
+                _ptr(grad_output), _ptr(grad_q), _ptr(grad_cbsr), *shape))
+    return grad_q, grad_cbsr
+
+
+def dot_attention_backward_route(num_heads: int, num_rows: int, num_e: int, k: int) -> str:
+    """How the backward of the fused dot-product attention should run: "fused", one
+    dot_attention_heads_backward call, or "rebuilt", dot_edge_alpha_heads and the stored path's
+    passes (edge_weight_grad_heads, H edge_softmax_backward, spgemm_forward_heads, two
+    sspmm_backward_heads).  Measured against exactly that sequence on the same inputs in the same
+    run (profiles/r20/dot_attention_bwd/), fused / rebuilt at H = 1, 2, 4, 8:
+    Reddit-sized k = 16 0.55, 0.56, 0.59, 0.80 and k = 32 0.58, 0.61, 0.66, 0.89; products-sized
+    k = 16 0.59, 0.58, 0.58, 0.78 and k = 32 0.62, 0.63, 0.64, 0.86, against spreads of the
+    rebuilt backward of 0.2 to 1.8 % -- a win past the spread at every point, smallest at eight
+    heads, where the staged rows leave two waves per SIMD -- and MaxKTransformerConv's training
+    step 0.71 to 0.94 of the step with the rebuilt backward.  So the rule has no threshold and
+    num_rows, num_e and k do not enter it: "fused" for every head count.  What it costs is
+    memory on a sparse graph: `out` [H, V, D] stays alive until this backward has run, and where
+    D exceeds the average degree it is larger than the [H, E] transients it replaces -- the
+    products-sized step peaks 2.7 to 17.0 GB above the step with the rebuilt backward (its
+    `out`: 2.5 GB per head) and 4.9 to 31.2 GB above the stored path, while the Reddit-sized
+    step peaks 0.3 to 1.2 GB below the rebuilt one from two heads on and below the stored path
+    too: "rebuilt" remains the memory-saving option on sparse graphs.
+    MAXK_DOT_ATTN_BWD=fused|rebuilt forces one.  Not wired into a default: MaxKTransformerConv's
+    `attention_backward` defaults to "rebuilt"."""
+    forced = os.environ.get("MAXK_DOT_ATTN_BWD", "")
+    if forced in ("fused", "rebuilt"):
+        return forced
+    return "fused"
 
 
 def heads_attention_route(num_heads: int, num_rows: int, num_e: int) -> Tuple[str, str]:

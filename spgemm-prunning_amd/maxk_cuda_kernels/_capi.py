@@ -110,6 +110,12 @@ SIGNATURES = {
     "maxk_dot_edge_alpha_heads": (ctypes.c_int, [_p, _p, _p, ctypes.c_float, _p, _p, _p, _p, _p,
                                                  _i64, _i64, _i64, _i32, _i32, _i32, _i32, _p, _sz,
                                                  _p]),
+    "maxk_dot_attention_heads_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32,
+                                                               _i32]),
+    "maxk_dot_attention_heads_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, ctypes.c_float, _p,
+                                                         _p, _p, _p, _p, _p, _p, _p, _i64, _i64,
+                                                         _i64, _i32, _i32, _i32, _i32, _p, _sz,
+                                                         _p]),
     "maxk_sspmm_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
     "maxk_sspmm_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                            _i32, _i32, _i32, _p, _sz, _p]),

@@ -116,14 +116,22 @@ class CSRGraph:
                                         topk_indices, dim, negative_slope, backward, dropout,
                                         seed)
 
-    def dot_attend_heads(self, topk_values, topk_indices, dim: int, q, scale: float):
+    def dot_attend_heads(self, topk_values, topk_indices, dim: int, q, scale: float,
+                         backward: str = "rebuilt"):
         """[H, V, dim]: scaled dot-product attention of H heads on the CBSR keys, from the
         queries q [H, V, dim] mapped into the feature space, with the score and the softmax
         inside the aggregation walk (maxk_dot_attention_heads): what maxk_dot_scores_heads, the
-        edge softmax per head and aggregate_heads give, without logits or alpha [H, E] stored;
-        alpha is a transient of the backward."""
+        edge softmax per head and aggregate_heads give, without logits or alpha [H, E] stored.
+        backward: "rebuilt" (alpha as a transient of the backward) or "fused" (one
+        dot_attention_heads_backward call, no [H, E] tensor in the backward either);
+        MAXK_DOT_ATTN_BWD=fused|rebuilt overrides it."""
+        if backward not in ("rebuilt", "fused"):
+            raise ValueError(f'backward must be "rebuilt" or "fused", got {backward!r}')
+        forced = os.environ.get("MAXK_DOT_ATTN_BWD", "")
+        if forced in ("fused", "rebuilt"):
+            backward = forced
         return maxk_dot_attention_heads(self.indptr, self.indices, q, topk_values, topk_indices,
-                                        dim, scale)
+                                        dim, scale, backward)
 
 
 class MaxK(Function):
@@ -641,17 +649,28 @@ class MaxKTransformerConv(nn.Module):
     CSRGraph.dot_attend_heads, which keeps the row statistics [H, V] instead and rebuilds alpha
     as a transient in the backward.  MAXK_DOT_ATTN=fused|stored overrides the argument.
 
+    attention_backward="fused" (with the fused attention only; the default is "rebuilt") runs
+    that backward as one mk.dot_attention_heads_backward call, with no [H, E] tensor in the
+    backward either; it keeps `agg` [H, V, in] alive until then.
+    MAXK_DOT_ATTN_BWD=fused|rebuilt overrides the argument; mk.dot_attention_backward_route has
+    the measurements.
+
     attn_drop: dropout of alpha after the softmax's normalisation, in training mode, under the
     mask of (seed, head, edge) (mk.edge_dropout_heads); forward(..., attn_seed=) fixes the seed.
     The stored path only: the fused walk has no dropout yet and raises a ValueError."""
 
     def __init__(self, in_feats: int, out_feats: int, num_heads: int, bias: bool = True,
-                 activation=None, attention: str = "stored", attn_drop: float = 0.0):
+                 activation=None, attention: str = "stored", attn_drop: float = 0.0,
+                 attention_backward: str = "rebuilt"):
         super().__init__()
         self.attn_drop = _check_attn_drop(attn_drop)
         if attention not in ("stored", "fused"):
             raise ValueError(f'attention must be "stored" or "fused", got {attention!r}')
+        if attention_backward not in ("rebuilt", "fused"):
+            raise ValueError('attention_backward must be "rebuilt" or "fused", got '
+                             f'{attention_backward!r}')
         self.attention = attention
+        self.attention_backward = attention_backward
         if not 1 <= int(num_heads) <= mk.MAX_HEADS:
             raise ValueError(f"num_heads must be in [1, {mk.MAX_HEADS}], got {num_heads}")
         self.in_feats, self.out_feats, self.num_heads = in_feats, out_feats, int(num_heads)
@@ -671,6 +690,13 @@ class MaxKTransformerConv(nn.Module):
         forced = os.environ.get("MAXK_DOT_ATTN", "")
         return forced if forced in ("fused", "stored") else self.attention
 
+    def attention_backward_mode(self) -> str:
+        """"fused" or "rebuilt", the backward of the fused attention: MAXK_DOT_ATTN_BWD when it
+        names one, else the `attention_backward` argument.  Without effect where attention_mode()
+        is "stored"."""
+        forced = os.environ.get("MAXK_DOT_ATTN_BWD", "")
+        return forced if forced in ("fused", "rebuilt") else self.attention_backward
+
     def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices,
                 attn_seed: Optional[int] = None):
         H, O, I = self.num_heads, self.out_feats, self.in_feats
@@ -683,7 +709,8 @@ class MaxKTransformerConv(nn.Module):
         # (W_q x_v) . (W_k x_u) = ((x_v W_q^T) W_k) . x_u: the query in the feature space
         q = torch.matmul(torch.matmul(x_sparse, Wq.transpose(1, 2)), Wk)  # [H, V, in]
         if fused:
-            agg = graph.dot_attend_heads(topk_values, topk_indices, I, q, self.scale)
+            agg = graph.dot_attend_heads(topk_values, topk_indices, I, q, self.scale,
+                                         self.attention_backward_mode())
         else:
             logits = maxk_dot_scores_heads(graph.indptr, graph.indices, q, topk_values,
                                            topk_indices, self.scale)

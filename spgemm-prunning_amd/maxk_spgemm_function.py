@@ -591,27 +591,47 @@ class MaxKDotAttentionHeadsFunction(Function):
     on them: edge_weight_grad_heads for the coefficients' gradient, edge_softmax_backward per head
     for the logits', spgemm_forward_heads on those for q, and for topk_values the sum of the
     aggregation's feature gradient (sspmm_backward_heads on the coefficients) and the scores'
-    (sspmm_backward_heads on the logits' gradient against q)."""
+    (sspmm_backward_heads on the logits' gradient against q).
+
+    backward="fused" (an eighth argument; "rebuilt", the above, is the default) saves `out` as
+    well and runs one maxk_cuda_kernels.dot_attention_heads_backward call instead: no tensor of
+    H * E elements in the backward either.  It falls back to the rebuilt backward when not both
+    gradients are needed, when the table is too large for the entry
+    (maxk_cuda_kernels.HEADS_MAX_COLS) and when MAXK_BWD_MODE forces a backward mode."""
 
     @staticmethod
-    def forward(ctx, graph_indptr, graph_indices, q, topk_values, topk_indices, dim_origin, scale):
+    def forward(ctx, graph_indptr, graph_indices, q, topk_values, topk_indices, dim_origin, scale,
+                backward="rebuilt"):
         _require_kernels()
+        if backward not in ("rebuilt", "fused"):
+            raise ValueError(f'backward must be "rebuilt" or "fused", got {backward!r}')
         indptr, indices, qf, vals, sel = _dot_inputs(graph_indptr, graph_indices, q, topk_values,
                                                      topk_indices)
         ctx.scale = float(scale)
         ctx.q_dtype = q.dtype
         out, row_max, row_sum = maxk_cuda_kernels.dot_attention_heads(
             indptr, indices, qf, vals, sel, int(dim_origin), ctx.scale)
-        ctx.save_for_backward(indptr, indices, qf, vals, sel, row_max, row_sum)
+        V, k = vals.shape
+        ctx.fused_bwd = (backward == "fused" and V < maxk_cuda_kernels.HEADS_MAX_COLS
+                         and maxk_cuda_kernels.graph_only_mode(k, indices.numel(), V) is not None)
+        if ctx.fused_bwd:
+            ctx.save_for_backward(indptr, indices, qf, vals, sel, row_max, row_sum, out)
+        else:
+            ctx.save_for_backward(indptr, indices, qf, vals, sel, row_max, row_sum)
         ctx.mark_non_differentiable(row_max, row_sum)
         return out, row_max, row_sum
 
     @staticmethod
     def backward(ctx, grad_output, _grad_max, _grad_sum):
-        indptr, indices, qf, vals, sel, row_max, row_sum = ctx.saved_tensors
+        indptr, indices, qf, vals, sel, row_max, row_sum = ctx.saved_tensors[:7]
         mk = maxk_cuda_kernels
         g = _f32_grad(grad_output)
         H, _, D = qf.shape
+        if ctx.fused_bwd and all(ctx.needs_input_grad[2:4]):
+            grad_q, grad_tv = mk.dot_attention_heads_backward(
+                indptr, indices, qf, vals, sel, ctx.saved_tensors[7], row_max, row_sum, g,
+                ctx.scale)
+            return None, None, grad_q.to(ctx.q_dtype), grad_tv, None, None, None, None
         alpha = mk.dot_edge_alpha_heads(indptr, indices, qf, vals, sel, D, ctx.scale, row_max,
                                         row_sum)
         grad_a = mk.edge_weight_grad_heads(indptr, indices, vals, sel, g)
@@ -628,18 +648,19 @@ class MaxKDotAttentionHeadsFunction(Function):
             grad_tv.add_(mk.sspmm_backward_heads(indptr, indices, grad_l, qf, sel),
                          alpha=ctx.scale)
         del alpha, grad_l
-        return None, None, grad_q, grad_tv, None, None, None
+        return None, None, grad_q, grad_tv, None, None, None, None
 
 
 def maxk_dot_attention_heads(graph_indptr, graph_indices, q, topk_values, topk_indices,
-                             dim_origin, scale):
+                             dim_origin, scale, backward="rebuilt"):
     """[H, V, dim_origin] = sum over a row's edges of softmax(scale * q[h, row] .
     scatter(topk)[col]) * scatter(topk)[col], for the H heads of one CSR graph, without logits or
     coefficients [H, E] being stored; gradients for q and topk_values
-    (MaxKDotAttentionHeadsFunction)."""
+    (MaxKDotAttentionHeadsFunction).  backward: "rebuilt" (the coefficients as a transient and
+    the stored path's passes) or "fused" (one dot_attention_heads_backward call)."""
     _require_kernels()
     return MaxKDotAttentionHeadsFunction.apply(graph_indptr, graph_indices, q, topk_values,
-                                               topk_indices, dim_origin, scale)[0]
+                                               topk_indices, dim_origin, scale, backward)[0]
 
 
 class MaxKSpmmWrapper:

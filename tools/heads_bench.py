@@ -56,6 +56,16 @@ within every iteration so all of them see the same clocks and cache state:
   step_fused / step_stored     MaxKTransformerConv forward plus backward, attention="fused"
                         against "stored", out_feats = D / H, with the peak memory of one step
 
+  dot_attention_bwd_fused    mk.dot_attention_heads_backward   one call
+                                                                    (--pairs dot_attention_bwd)
+  dot_attention_bwd_rebuilt  exactly what it replaces: mk.dot_edge_alpha_heads,
+                        mk.edge_weight_grad_heads, H x mk.edge_softmax_backward,
+                        mk.spgemm_forward_heads and the scale, two mk.sspmm_backward_heads and
+                        the add_: MaxKDotAttentionHeadsFunction's rebuilt backward
+  step_stored / step_fused_rebuilt / step_fused_fused   MaxKTransformerConv forward plus backward
+                        for attention stored, fused with the rebuilt backward and fused with the
+                        fused backward, with the peak memory of one step of each
+
 It reports the medians, the ratio heads / calls of each pair, and the run-to-run spread of the
 single-head baselines in this run, (max - min) / median over the iterations: the heads kernel
 counts as faster only where 1 - ratio exceeds that spread.  For the feature gradient it also
@@ -69,6 +79,8 @@ timed.  Writes one JSON file and prints it.
   python tools/heads_bench.py --pairs attention_dropout --heads 1,2,4,8 --out FILE
   python tools/heads_bench.py --pairs dot_attention --graphs reddit:16,reddit:32,products:16,products:32
                               --heads 1,2,4,8 --out FILE
+  python tools/heads_bench.py --pairs dot_attention_bwd --graphs reddit:16,reddit:32,products:16,products:32
+                              --heads 1,2,4,8 --out profiles/r20/dot_attention_bwd/bench.json
 """
 import argparse
 import json
@@ -760,6 +772,130 @@ def run_dot_attention(name, k, D, H, iters, warmup, seed, dev):
     return r
 
 
+def run_dot_attention_bwd(name, k, D, H, iters, warmup, seed, dev):
+    """mk.dot_attention_heads_backward against exactly the rebuilt sequence it replaces
+    (MaxKDotAttentionHeadsFunction.backward), on the same inputs, alternating inside every
+    iteration; then MaxKTransformerConv's training step for attention stored, fused with the
+    rebuilt backward and fused with the fused one, and the peak memory of one step of each."""
+    import maxk_layers as ML
+    V = bench.maxk_graph.PRESETS[name]["V"]
+    row_ptr, col = _graph(name, seed, dev)
+    E = col.numel()
+    gen = torch.Generator(device=dev).manual_seed(655)
+    q = torch.randn(H, V, D, generator=gen, device=dev)
+    cv, ci = mk.topk_cbsr(torch.rand(V, D, generator=gen, device=dev), k)
+    G = torch.randn(H, V, D, generator=gen, device=dev)
+    scale = float(D // H) ** -0.5
+    out, m, z = mk.dot_attention_heads(row_ptr, col, q, cv, ci, D, scale, validate=True)
+    plan = mk.transpose_plan(col, V)  # once per graph, as in training: not part of either side
+    keep = {}
+
+    def bwd_fused():
+        keep["fused"] = mk.dot_attention_heads_backward(row_ptr, col, q, cv, ci, out, m, z, G,
+                                                        scale, validate=False, plan=plan)
+
+    def bwd_rebuilt():  # MaxKDotAttentionHeadsFunction.backward, backward="rebuilt"
+        alpha = mk.dot_edge_alpha_heads(row_ptr, col, q, cv, ci, D, scale, m, z, validate=False)
+        grad_a = mk.edge_weight_grad_heads(row_ptr, col, cv, ci, G, validate=False)
+        grad_l = torch.empty_like(grad_a)
+        for h in range(H):
+            mk.edge_softmax_backward(row_ptr, alpha[h], grad_a[h], out=grad_l[h])
+        del grad_a
+        g_q = mk.spgemm_forward_heads(row_ptr, col, grad_l, cv, ci, D, validate=False).mul_(scale)
+        g_tv = mk.sspmm_backward_heads(row_ptr, col, alpha, G, ci, validate=False, plan=plan)
+        g_tv.add_(mk.sspmm_backward_heads(row_ptr, col, grad_l, q, ci, validate=False, plan=plan),
+                  alpha=scale)
+        keep["rebuilt"] = (g_q, g_tv)
+
+    ops = (("dot_attention_bwd_fused", bwd_fused), ("dot_attention_bwd_rebuilt", bwd_rebuilt))
+    for _ in range(warmup):
+        for _, fn in ops:
+            fn()
+    torch.cuda.synchronize()
+    ts = {n: [] for n, _ in ops}
+    for _ in range(iters):
+        for n, fn in ops:
+            ts[n].append(timed(fn))
+    s = {n: summary(t) for n, t in ts.items()}
+    r = dict(kind="dot_attention_bwd", graph=name, V=V, E=E, D=D, k=k, H=H, scale=scale, **s)
+    for what, a, b in zip(("grad_q", "grad_cbsr"), keep["fused"], keep["rebuilt"]):
+        r[f"{what}_max_diff_over_max"] = float((a - b).abs().max() / b.abs().max())
+    HP = 2 if H <= 2 else 4 if H <= 4 else 8
+    r["workspace_bytes_fused"] = int(mk._lib().maxk_dot_attention_heads_backward_workspace_size(
+        V, V, E, D, k, H, 0))
+    r["T_bytes"], r["glT_bytes"], r["out_bytes"] = 4 * (E + 1) * k, 4 * HP * E, 4 * H * V * D
+    r["alpha_bytes"] = 4 * H * E
+    for n, fn in ops:  # the peak of one backward over what is resident before it
+        keep.clear()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        r[f"{n}_peak_over_resident_bytes"] = int(torch.cuda.max_memory_allocated() - base)
+    keep.clear()
+    del out, m, z, G, q
+    torch.cuda.empty_cache()
+
+    graph = ML.CSRGraph(row_ptr, col)
+    torch.manual_seed(7)
+    conv = ML.MaxKTransformerConv(D, D // H, H).to(dev)
+    xs, vals, idx = ML.maxk(torch.rand(V, D, device=dev), k)
+    xs = xs.detach().requires_grad_(True)
+    vals = vals.detach().requires_grad_(True)
+    modes = {"stored": ("stored", "rebuilt"), "fused_rebuilt": ("fused", "rebuilt"),
+             "fused_fused": ("fused", "fused")}
+
+    def step(mode):
+        conv.attention, conv.attention_backward = modes[mode]
+        conv.zero_grad(set_to_none=True)
+        xs.grad = vals.grad = None
+        conv(graph, xs, vals, idx).sum().backward()
+
+    saved = {v: os.environ.pop(v, None) for v in ("MAXK_DOT_ATTN", "MAXK_DOT_ATTN_BWD")}
+    try:
+        for _ in range(warmup):
+            for mode in modes:
+                step(mode)
+        torch.cuda.synchronize()
+        tl = {mode: [] for mode in modes}
+        for _ in range(iters):
+            for mode in modes:
+                tl[mode].append(timed(lambda: step(mode)))
+        for mode in modes:  # the peak of one step, the other modes' buffers released
+            conv.zero_grad(set_to_none=True)
+            xs.grad = vals.grad = None
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            step(mode)
+            torch.cuda.synchronize()
+            r[f"step_{mode}_peak_bytes"] = int(torch.cuda.max_memory_allocated())
+            r[f"step_{mode}_peak_over_resident_bytes"] = int(torch.cuda.max_memory_allocated()
+                                                             - base)
+    finally:
+        for v, x in saved.items():
+            if x is not None:
+                os.environ[v] = x
+    sl = {f"step_{mode}": summary(t) for mode, t in tl.items()}
+    r.update(sl)
+    r["ratio_dot_attention_bwd_fused_to_rebuilt"] = round(
+        s["dot_attention_bwd_fused"]["median_ms"] / s["dot_attention_bwd_rebuilt"]["median_ms"], 4)
+    r["dot_attention_bwd_fused_faster"] = bool(
+        1.0 - r["ratio_dot_attention_bwd_fused_to_rebuilt"]
+        > s["dot_attention_bwd_rebuilt"]["spread"])
+    r["dot_attention_bwd_fused_slower"] = bool(
+        r["ratio_dot_attention_bwd_fused_to_rebuilt"] - 1.0
+        > s["dot_attention_bwd_rebuilt"]["spread"])
+    for a, b in (("fused_fused", "fused_rebuilt"), ("fused_fused", "stored"),
+                 ("fused_rebuilt", "stored")):
+        r[f"ratio_step_{a}_to_{b}"] = round(
+            sl[f"step_{a}"]["median_ms"] / sl[f"step_{b}"]["median_ms"], 4)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--graphs", default="reddit:16,products:32")
@@ -797,6 +933,9 @@ def main():
             if "dot_attention" in asked:
                 rs.append(run_dot_attention(name, int(k), args.dim, H, args.iters, args.warmup,
                                             args.seed, dev))
+            if "dot_attention_bwd" in asked:
+                rs.append(run_dot_attention_bwd(name, int(k), args.dim, H, args.iters,
+                                                args.warmup, args.seed, dev))
             if "layer" in asked and H >= 2:
                 rs.append(run_layer(name, int(k), args.dim, H, args.iters, args.warmup,
                                     args.seed, dev))
