@@ -983,6 +983,67 @@ int maxk_pull_plan(const int32_t *row_ptr, const int32_t *col_idx, const float *
                    size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Backward, pull form, stream path (dim_k % 4 == 0): the same sums as maxk_sspmm_backward_pull
+ * with one workgroup per (destination bucket, part) for the whole call.  A bucket's entries
+ * are walked front to back in CSR order, the fp64 sums stay in LDS until the workgroup stores
+ * its own rows of grad_cbsr: no tile partials, no reduce kernel.  Every row of grad_cbsr is
+ * written (zeros where no edge arrives).  Two runs agree as for the tiled pull; against it the
+ * result differs by one fp32 rounding of an fp64 sum (the tiled pull rounds each slice's sum).
+ *
+ * maxk_pull_stream_buckets: the number of buckets the path uses for a shape, or 0 where it does
+ *   not apply and the tiled pull stays.  With cap = 2^maxk_pull_shift(dim_k) and H parts per
+ *   bucket, the fewest workgroups are ceil(num_cols / cap) * H; they are rounded up to whole
+ *   rounds of `cus` workgroups (cus <= 0: the current device's CU count), which narrows the mean
+ *   bucket; 0 when that narrows it by more than 12.5 %, when dim_k % 4 or dim_origin % 4 != 0,
+ *   when G has 2^31 bytes or more (num_rows * dim_origin * 4), when num_e >= 2^28 (num_e < 0:
+ *   unknown, not checked) or when the bits of num_rows - 1 plus maxk_pull_shift(dim_k) exceed
+ *   32.  Callable without a device when cus > 0.
+ * maxk_pull_stream_plan (once per graph, edge_val, dim_k, n_buckets and slices):
+ *   bucket_col[n_buckets + 1], increasing from 0 to num_cols, every width <= cap, chosen on the
+ *   prefix sum of the in-degrees so that the buckets hold as nearly as possible equal edge
+ *   counts (a width that balance would push past cap is clamped); grp_ptr[n_buckets + 1], the
+ *   buckets' entry ranges; ent[2 * num_e], per bucket the edges ordered by (slice of
+ *   ceil(num_rows / slices) source rows, CSR order), one uint32 pair each: {row <<
+ *   maxk_pull_shift(dim_k) | column - bucket_col[b], bits of edge_val}.  n_buckets * cap >=
+ *   num_cols.  The slices only widen the sort key (CSR order is row order, so a bucket's
+ *   entries come out in CSR order whatever their count); maxk_pull_stream_slices gives 1.
+ * maxk_pull_stream_entries_scale: ent_out = ent with every weight divided by its row's
+ *   row_div, once per (plan, divisor), so the backward gathers G itself.
+ * maxk_sspmm_backward_pull_stream: the backward over such a plan; n_buckets need not come from
+ *   maxk_pull_stream_buckets.  With row_div != NULL it gathers from a G / row_div copy in the
+ *   workspace, as the tiled pull.
+ * Memory: the workspace (maxk_sspmm_backward_pull_stream_workspace_size) holds the G / row_div
+ *   copy (num_rows x dim_origin floats) and 2 x num_cols x dim_k bytes of slot-ordered selectors
+ *   and their map; the tiled pull's slices x num_cols x dim_k floats of tile partials (417 MB
+ *   for a Reddit-sized graph at dim_k = 16) are not needed.  The plan takes what a pull plan
+ *   takes (8 bytes per edge) plus 8 bytes per bucket.
+ * Replaces the same reference kernels as maxk_sspmm_backward (spmm_maxk_backward.cu:15-121).
+ * ------------------------------------------------------------------------- */
+int64_t maxk_pull_stream_buckets(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                 int32_t dim_origin, int32_t dim_k, int32_t cus);
+int maxk_pull_stream_slices(int64_t num_rows, int64_t num_cols, int32_t dim_origin,
+                            int32_t dim_k);
+size_t maxk_pull_stream_plan_workspace_size(int64_t num_cols, int64_t num_e, int32_t n_buckets,
+                                            int32_t slices);
+int maxk_pull_stream_plan(const int32_t *row_ptr, const int32_t *col_idx, const float *edge_val,
+                          int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_k,
+                          int32_t n_buckets, int32_t slices, int32_t *bucket_col,
+                          int32_t *grp_ptr, uint32_t *ent, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int maxk_pull_stream_entries_scale(const uint32_t *ent, int64_t num_e, int64_t num_rows,
+                                   int32_t dim_k, const float *row_div, uint32_t *ent_out,
+                                   void *stream);
+size_t maxk_sspmm_backward_pull_stream_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                      int32_t dim_origin, int32_t dim_k);
+int maxk_sspmm_backward_pull_stream(const float *grad_out, const float *row_div,
+                                    const uint8_t *cbsr_idx, const int32_t *bucket_col,
+                                    const int32_t *grp_ptr, const uint32_t *ent,
+                                    int32_t n_buckets, float *grad_cbsr, int64_t num_rows,
+                                    int64_t num_cols, int64_t num_e, int32_t dim_origin,
+                                    int32_t dim_k, void *workspace, size_t workspace_bytes,
+                                    void *stream);
+
+/* ---------------------------------------------------------------------------
  * Dense route (r05): wide top-k, dim_k >= dim_origin / 2 at dim_origin % 4 == 0,
  * dim_origin <= 128 (MAXK_DENSE_DMAX), dim_k % 4 == 0.  A CBSR row then carries as many bytes as
  * the dense row, so both directions aggregate dense rows.  Replaces the same reference kernels

@@ -292,7 +292,9 @@ __global__ __launch_bounds__(kBlock) void pull_sel4_kernel(const uint8_t *__rest
 
 // One tile's entry loop of pull_q_kernel: adds the tile's n_e entries (ers)
 // into the fp64 accumulator, gathering from the slice's G' rows (grs).
-template <int LR, int U, bool FULLD, int VPL>
+// GROW (the stream form): an entry's key is {global row << shift | column in the bucket} and
+// grs covers all of G', so one loop walks a bucket's entries of every slice.
+template <int LR, int U, bool FULLD, int VPL, bool GROW = false>
 __device__ __forceinline__ void pull_q_entries(double *acc, const uint8_t *sel_lds,
                                                __amdgpu_buffer_rsrc_t grs,
                                                __amdgpu_buffer_rsrc_t ers, int n_e, int D,
@@ -361,7 +363,9 @@ __device__ __forceinline__ void pull_q_entries(double *acc, const uint8_t *sel_l
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             ok[u] = eb + u * EPI < n_e && qok;
-            const int d = ok[u] ? (int)(ex[u] >> 16) : idle;
+            const int d = !ok[u] ? idle
+                          : GROW ? (int)(ex[u] & ((1u << shift) - 1u))
+                                 : (int)(ex[u] >> 16);
             dc[u] = d * ks + VPL * q * ok[u];
             const uint8_t *sp = sel_lds + d * kp + (ok[u] ? q * VPL : 0);
             if constexpr (VPL == 8)
@@ -374,7 +378,8 @@ __device__ __forceinline__ void pull_q_entries(double *acc, const uint8_t *sel_l
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const uint32_t ro = ok[u] ? (ex[u] & 0xffffu) * Db : 0x80000000u;
+            const uint32_t ro =
+                ok[u] ? (GROW ? ex[u] >> shift : ex[u] & 0xffffu) * Db : 0x80000000u;
 #pragma unroll
             for (int i = 0; i < VPL; ++i) {
                 const uint32_t c = VPL == 8 ? (uint32_t)(sv[u] >> (8 * i)) & 255u
@@ -443,12 +448,11 @@ constexpr int kSelRegs = 2;
 struct PullSel {
     uint4 v[kSelRegs];
 };
-__device__ __forceinline__ PullSel pull_sel_load(const uint8_t *__restrict__ sel_q, int64_t c0,
-                                                 int64_t num_cols, int k, int kp, int h,
-                                                 int shift) {
+// ... of the `rows` destinations from column c0 on (the pieces past them hold zeros)
+__device__ __forceinline__ PullSel pull_sel_load_rows(const uint8_t *__restrict__ sel_q,
+                                                      int64_t c0, int rows, int k, int kp, int h) {
     PullSel r;
     const int tid = threadIdx.x;
-    const int rows = num_cols - c0 < (1 << shift) ? (int)(num_cols - c0) : (1 << shift);
     const uint8_t *__restrict__ selg = sel_q + c0 * k + h * kp;
     // piece i: destination i / ppr, bytes [16 * (i % ppr), +16) of its kp (ppr = kp / 16), or
     // for kp < 16 whole 16-B groups of 16 / kp destinations packed from their kp-byte parts
@@ -476,6 +480,12 @@ __device__ __forceinline__ PullSel pull_sel_load(const uint8_t *__restrict__ sel
         r.v[m] = x;
     }
     return r;
+}
+__device__ __forceinline__ PullSel pull_sel_load(const uint8_t *__restrict__ sel_q, int64_t c0,
+                                                 int64_t num_cols, int k, int kp, int h,
+                                                 int shift) {
+    const int rows = num_cols - c0 < (1 << shift) ? (int)(num_cols - c0) : (1 << shift);
+    return pull_sel_load_rows(sel_q, c0, rows, k, kp, h);
 }
 __device__ __forceinline__ void pull_sel_store(uint8_t *sel_lds, const PullSel &r, int kp,
                                                int shift) {
@@ -548,6 +558,81 @@ __global__ __launch_bounds__(1024) void pull_q_kernel(
     pull_q_entries<LR, U, FULLD, VPL>(acc, sel_lds, grs, ers, p.s1 - p.s0, D, kp, shift);
     __syncthreads();
     pull_flush(acc, tile_out, ti, h, k, kp, shift);
+}
+
+// The stream form (maxk_sspmm_backward_pull_stream): one workgroup per (bucket, part) for the
+// whole call.  The stream plan's buckets [bucket_col[b], bucket_col[b + 1]) hold about equal
+// entry counts, as many buckets as fill whole rounds of one workgroup per CU; a bucket's
+// entries ent[grp_ptr[b] .. grp_ptr[b + 1]) are in CSR order and carry their global source
+// row, so the workgroup walks them front to back through one descriptor over G'.  The
+// workgroups of a round start together with equal work and so sweep the rows of G' side by
+// side, which is what lets an XCD's L2 serve a row to all of them; no workgroup waits for
+// another.  Inside a workgroup the 16 waves share no data and nothing keeps them together
+// (without the barrier below they drift tens of thousands of rows apart and the L2 hit rate
+// falls to 43 %), so the walk goes in runs of MAXK_PULL_STREAM_RUN entries with a
+// workgroup barrier after each.  The fp64 sums never leave LDS: there are no tile partials and
+// no reduce, the workgroup stores its rows of grad_cbsr itself (slot f of part h to l =
+// lmap[c * k + h * kp + f]).  XCD x runs part x % H of its buckets, so the workgroups that
+// share an L2 gather the same share of every row's columns.
+#ifndef MAXK_PULL_STREAM_RUN  // entries between two workgroup barriers (Reddit k = 16: 4096 /
+#define MAXK_PULL_STREAM_RUN 16384  // 16384 / 65536 / 262144 / none = 1.93 / 1.81 / 1.84 / 2.22 / 2.84 ms)
+#endif
+template <int LR, int U, bool FULLD, int VPL, int STREAM>
+__global__ __launch_bounds__(1024) void pull_q_kernel(
+    const float *__restrict__ Gp, const uint8_t *__restrict__ sel_q,
+    const uint8_t *__restrict__ lmap, const int32_t *__restrict__ bucket_col,
+    const int32_t *__restrict__ grp_ptr, const uint2 *__restrict__ ent,
+    float *__restrict__ grad_cbsr, int64_t num_cols, int n_buckets, int64_t num_rows, int D,
+    int k, int kp, int shift) {
+    static_assert(STREAM == 1, "the stream form");
+    extern __shared__ double acc[];  // [ks << shift], then [kp << shift] selector bytes
+    const int tid = threadIdx.x;
+    const int ks = pull_ks(kp, shift);
+    const int H = k / kp;
+    int b, h;
+    if (kXcds % H == 0) {
+        const int x = blockIdx.x % kXcds, per = gridDim.x / kXcds;
+        h = x % H;
+        b = (x / H) * per + blockIdx.x / kXcds;
+        if (b >= n_buckets) return;  // the XCD grid's padding
+    } else {
+        const int tp = xcd_contiguous_block(blockIdx.x, gridDim.x);
+        if (tp >= n_buckets * H) return;
+        b = tp / H, h = tp % H;
+    }
+    // a bucket wider than the accumulator or past the table cannot come from the plan call;
+    // clamped all the same, so no plan can make the kernel write outside LDS or grad_cbsr
+    const int64_t c0 = bucket_col[b];
+    int64_t c1 = bucket_col[b + 1];
+    c1 = c1 > num_cols ? num_cols : c1;
+    int width = c1 > c0 && c0 >= 0 ? (int)(c1 - c0) : 0;
+    width = width > (1 << shift) ? (1 << shift) : width;
+    const int s0 = grp_ptr[b];
+    const int n_e = width > 0 && grp_ptr[b + 1] > s0 ? grp_ptr[b + 1] - s0 : 0;
+    uint8_t *sel_lds = reinterpret_cast<uint8_t *>(acc + (ks << shift));
+    for (int i = tid; i < (ks << shift); i += 1024) acc[i] = 0.0;
+    pull_sel_store(sel_lds, pull_sel_load_rows(sel_q, c0, width, k, kp, h), kp, shift);
+    __syncthreads();
+    const auto grs = wave_buffer(Gp, (uint32_t)num_rows * (uint32_t)D * 4u);
+    constexpr int RUN = MAXK_PULL_STREAM_RUN;
+    for (int e0 = 0; e0 < n_e; e0 += RUN) {  // n_e is the workgroup's: every wave meets the barrier
+        const int n = n_e - e0 < RUN ? n_e - e0 : RUN;
+        const auto ers = wave_buffer(ent + s0 + e0, (uint32_t)n * 8u);
+        pull_q_entries<LR, U, FULLD, VPL, true>(acc, sel_lds, grs, ers, n, D, kp, shift);
+        __syncthreads();
+    }
+    const int w4 = kp / 4;
+    for (int i4 = tid; i4 < width * w4; i4 += 1024) {
+        const int d = i4 / w4, s4 = i4 % w4;
+        const double *a = &acc[d * ks + 4 * s4];
+        const size_t r0 = (size_t)(c0 + d) * k;
+        const uint32_t m = *reinterpret_cast<const uint32_t *>(lmap + r0 + h * kp + 4 * s4);
+        float *row = grad_cbsr + r0;
+        row[m & 255u] = (float)a[0];
+        row[(m >> 8) & 255u] = (float)a[1];
+        row[(m >> 16) & 255u] = (float)a[2];
+        row[m >> 24] = (float)a[3];
+    }
 }
 
 // grad_cbsr rows of bucket j = the sum of its slices' tiles, in slice order.  With lmap
@@ -650,6 +735,29 @@ PullLayout pull_layout(int64_t num_rows, int64_t num_cols, int D, int k, int64_t
     return L;
 }
 
+// pull_q_kernel's values per lane: 4 (one u32 selector word per lane; 2 lanes per entry for
+// 8-slot parts), 8 for k = 8 (one lane per entry, one u64 selector word; MAXK_PULL_VPL8)
+int pull_vpl(int kp, int parts) {
+    return kp != 8 ? 4 : MAXK_PULL_VPL8 ? MAXK_PULL_VPL8 : parts == 1 ? 8 : 4;
+}
+
+// The slot-ordered selectors sel_q and their l map lm of every destination (pull_sel_kernel).
+int launch_pull_sel(const uint8_t *cbsr_idx, uint8_t *sel_q, uint8_t *lm, int64_t num_cols, int k,
+                    int kp, int vpl, hipStream_t s) {
+    if (MAXK_PULL_SEL4 && (reinterpret_cast<uintptr_t>(cbsr_idx) & 3) == 0) {
+        const int nd4 = kBlock / (k / 4);
+        hipLaunchKernelGGL(pull_sel4_kernel, dim3((unsigned)ceil_div(num_cols, nd4)),
+                           dim3(kBlock), 0, s, cbsr_idx, sel_q, lm, num_cols, k, kp, vpl);
+        MAXK_LAUNCHED("pull_sel4_kernel");
+    } else {
+        const int nd = kBlock / k;
+        hipLaunchKernelGGL(pull_sel_kernel, dim3((unsigned)ceil_div(num_cols, nd)),
+                           dim3(kBlock), 0, s, cbsr_idx, sel_q, lm, num_cols, k, kp, vpl);
+        MAXK_LAUNCHED("pull_sel_kernel");
+    }
+    return MAXK_OK;
+}
+
 int pull_impl(const float *grad_out, const float *row_div, const uint8_t *cbsr_idx,
               const int32_t *tile_ptr, const uint32_t *ent, int32_t bucket_shift, int32_t slices,
               bool listed, const int32_t *tile_list, int32_t n_list, const int32_t *bucket_ptr,
@@ -718,22 +826,10 @@ int pull_impl(const float *grad_out, const float *row_div, const uint8_t *cbsr_i
         const size_t lds_q = pull_lds_bytes(pull_ks(kp, bucket_shift), kp, bucket_shift);
         uint8_t *sel_q = reinterpret_cast<uint8_t *>(ws + L.sel_off);
         uint8_t *lm = reinterpret_cast<uint8_t *>(ws + L.lmap_off);
-        const int nd = kBlock / k;
-        // values per lane: 4 (one u32 selector word per lane; 2 lanes per entry for 8-slot
-        // parts), 8 for k = 8 (one lane per entry, one u64 selector word; MAXK_PULL_VPL8)
-        const int vpl = kp != 8 ? 4 : MAXK_PULL_VPL8 ? MAXK_PULL_VPL8 : parts == 1 ? 8 : 4;
+        const int vpl = pull_vpl(kp, parts);
         lmap = lm;
         if (!front) goto reduce;
-        if (MAXK_PULL_SEL4 && (reinterpret_cast<uintptr_t>(cbsr_idx) & 3) == 0) {
-            const int nd4 = kBlock / (k / 4);
-            hipLaunchKernelGGL(pull_sel4_kernel, dim3((unsigned)ceil_div(num_cols, nd4)),
-                               dim3(kBlock), 0, s, cbsr_idx, sel_q, lm, num_cols, k, kp, vpl);
-            MAXK_LAUNCHED("pull_sel4_kernel");
-        } else {
-            hipLaunchKernelGGL(pull_sel_kernel, dim3((unsigned)ceil_div(num_cols, nd)),
-                               dim3(kBlock), 0, s, cbsr_idx, sel_q, lm, num_cols, k, kp, vpl);
-            MAXK_LAUNCHED("pull_sel_kernel");
-        }
+        if (int rc = launch_pull_sel(cbsr_idx, sel_q, lm, num_cols, k, kp, vpl, s)) return rc;
         const int64_t work = tiles * parts;
         const bool fulld = dim_origin == kMaxDim;
         const unsigned grid = (unsigned)(MAXK_PULL_XCD ? xcd_grid(work) : work);
@@ -782,10 +878,136 @@ reduce:
     MAXK_LAUNCHED("pull_reduce_kernel");
     return MAXK_OK;
 }
+
+// ---- the stream form -------------------------------------------------------------------
+// Largest share, in thousandths, by which the stream form may narrow the mean bucket against
+// the tiled form's 2^shift columns (whole rounds of workgroups need more, narrower buckets, and
+// a source row then meets more of them).  Measured at 109 (Reddit-sized, 114 -> 128 buckets:
+// DESIGN 5.2); nothing wider has been measured, so nothing wider is accepted.
+#ifndef MAXK_PULL_STREAM_NARROW
+#define MAXK_PULL_STREAM_NARROW 125
+#endif
+
+int64_t stream_buckets(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, int k,
+                       int64_t cus) {
+    if (!MAXK_PULL_Q || MAXK_PULL_STREAM_NARROW <= 0) return 0;
+    if (num_rows <= 0 || num_cols <= 0 || D <= 0 || D > kMaxDim || D % 4 || k <= 0 || k > D || k % 4)
+        return 0;
+    if (num_rows >= (1LL << 31) || num_cols >= (1LL << 31) || num_cols * (int64_t)k >= (1LL << 31))
+        return 0;
+    const int shift = maxk_pull_shift(k);
+    const int H = shift >= 4 && shift <= 15 ? pull_parts(k, shift) : 0;
+    if (H <= 0) return 0;
+    // gather offsets row * D * 4 + column * 4 stay below the "no entry" offset 2^31, far inside
+    // the 2^32 a descriptor over G' reaches; entry offsets are 32-bit as well
+    if (num_rows * D * 4 >= (1LL << 31) || num_e >= (1LL << 28)) return 0;
+    int row_bits = 0;
+    while ((1LL << row_bits) < num_rows) ++row_bits;
+    if (row_bits + shift > 32) return 0;
+    if (cus <= 0) cus = device_cus();
+    const int64_t nb_min = (num_cols + (1LL << shift) - 1) >> shift;
+    const int64_t rounds = (nb_min * H + cus - 1) / cus;
+    const int64_t nb = rounds * cus / H;
+    if (nb < nb_min || nb * H >= (1LL << 24)) return 0;
+    return (nb - nb_min) * 1000 <= nb * MAXK_PULL_STREAM_NARROW ? nb : 0;
+}
+
+int pull_stream_impl(const float *grad_out, const float *row_div, const uint8_t *cbsr_idx,
+                     const int32_t *bucket_col, const int32_t *grp_ptr, const uint32_t *ent,
+                     int32_t n_buckets, float *grad_cbsr, int64_t num_rows, int64_t num_cols,
+                     int64_t num_e, int32_t dim_origin, int32_t dim_k, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+    if (int rc = check_common(num_rows, num_cols, num_e, dim_origin, dim_k, 0)) return rc;
+    const int k = dim_k;
+    MAXK_REQUIRE(MAXK_PULL_Q && k % 4 == 0 && dim_origin % 4 == 0,
+                 "stream pull needs dim_k %% 4 == 0 and dim_origin %% 4 == 0, got %d, %d", k,
+                 dim_origin);
+    const int shift = maxk_pull_shift(k);
+    const int parts = shift >= 4 && shift <= 15 ? pull_parts(k, shift) : 0;
+    MAXK_REQUIRE(parts > 0, "no part count fits dim_k %d", k);
+    MAXK_REQUIRE(num_rows * dim_origin * 4 < (1LL << 31), "stream pull: G of 2 GiB or more");
+    MAXK_REQUIRE(num_e < (1LL << 28), "stream pull: 2^28 entries or more");
+    int row_bits = 0;
+    while ((1LL << row_bits) < num_rows) ++row_bits;
+    MAXK_REQUIRE(row_bits + shift <= 32, "stream pull: %d row bits + %d column bits exceed 32",
+                 row_bits, shift);
+    MAXK_REQUIRE(n_buckets >= 1 && (int64_t)n_buckets * parts < (1LL << 24) &&
+                     ((int64_t)n_buckets << shift) >= num_cols,
+                 "n_buckets %d out of range", n_buckets);
+    hipStream_t s = as_stream(stream);
+    if (num_cols == 0) return MAXK_OK;
+    MAXK_REQUIRE(grad_cbsr && bucket_col && grp_ptr && cbsr_idx,
+                 "grad_cbsr/bucket_col/grp_ptr/selector pointers must not be NULL");
+    MAXK_REQUIRE(num_e == 0 || (grad_out && ent), "grad/plan pointers must not be NULL");
+    const PullLayout L = pull_layout(num_rows, num_cols, dim_origin, k, 0, shift);
+    MAXK_REQUIRE(workspace && workspace_bytes >= L.total,
+                 "workspace too small: need %zu bytes, got %zu", L.total, workspace_bytes);
+    char *ws = reinterpret_cast<char *>(workspace);
+    const float *Gp = grad_out;
+    if (row_div && num_rows > 0 && num_e > 0) {
+        const int64_t n4 = num_rows * dim_origin / 4;
+        hipLaunchKernelGGL(gprime_kernel, dim3((unsigned)ceil_div(n4, kBlock)), dim3(kBlock), 0,
+                           s, grad_out, row_div, reinterpret_cast<float *>(workspace), n4,
+                           dim_origin / 4);
+        MAXK_LAUNCHED("gprime_kernel");
+        Gp = reinterpret_cast<const float *>(workspace);
+    }
+    const int kp = k / parts;
+    const int vpl = pull_vpl(kp, parts);
+    uint8_t *sel_q = reinterpret_cast<uint8_t *>(ws + L.sel_off);
+    uint8_t *lm = reinterpret_cast<uint8_t *>(ws + L.lmap_off);
+    if (int rc = launch_pull_sel(cbsr_idx, sel_q, lm, num_cols, k, kp, vpl, s)) return rc;
+    const size_t lds_q = pull_lds_bytes(pull_ks(kp, shift), kp, shift);
+    const unsigned grid = (unsigned)xcd_grid((int64_t)n_buckets * parts);
+    const bool fulld = dim_origin == kMaxDim;
+    const int lr = vpl == 4 ? lanes_per_edge(kp / 4) : kp / vpl;
+    const bool ok = with_lanes(lr, [&](auto lr_c) {
+        with_const<2, 4, 8>(vpl, [&](auto vpl_c) {
+            with_const<0, 1>(fulld, [&](auto fd_c) {
+                constexpr int LR = decltype(lr_c)::value, VPL = decltype(vpl_c)::value;
+                if constexpr (VPL == 4 || LR * VPL == 8)
+                    hipLaunchKernelGGL(
+                        (pull_q_kernel<LR, MAXK_PULL_QU, decltype(fd_c)::value, VPL, 1>),
+                        dim3(grid), dim3(1024), lds_q, s, Gp, sel_q, lm, bucket_col, grp_ptr,
+                        reinterpret_cast<const uint2 *>(ent), grad_cbsr, num_cols, (int)n_buckets,
+                        num_rows, dim_origin, k, kp, shift);
+            });
+        });
+    });
+    if (!ok) return bad_lanes(lr);
+    MAXK_LAUNCHED("pull_q_kernel");
+    return MAXK_OK;
+}
 }  // namespace
 }  // namespace maxk
 
 using namespace maxk;
+
+extern "C" int64_t maxk_pull_stream_buckets(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                            int32_t dim_origin, int32_t dim_k, int32_t cus) {
+    return stream_buckets(num_rows, num_cols, num_e, dim_origin, dim_k, cus);
+}
+
+extern "C" size_t maxk_sspmm_backward_pull_stream_workspace_size(int64_t num_rows,
+                                                                 int64_t num_cols,
+                                                                 int32_t dim_origin,
+                                                                 int32_t dim_k) {
+    if (num_rows < 0 || num_cols < 0 || dim_origin <= 0 || dim_k <= 0) return 0;
+    return pull_layout(num_rows, num_cols, dim_origin, dim_k, 0, 0).total;
+}
+
+extern "C" int maxk_sspmm_backward_pull_stream(const float *grad_out, const float *row_div,
+                                               const uint8_t *cbsr_idx, const int32_t *bucket_col,
+                                               const int32_t *grp_ptr, const uint32_t *ent,
+                                               int32_t n_buckets, float *grad_cbsr,
+                                               int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                               int32_t dim_origin, int32_t dim_k, void *workspace,
+                                               size_t workspace_bytes, void *stream) {
+    clear_error();
+    return pull_stream_impl(grad_out, row_div, cbsr_idx, bucket_col, grp_ptr, ent, n_buckets,
+                            grad_cbsr, num_rows, num_cols, num_e, dim_origin, dim_k, workspace,
+                            workspace_bytes, stream);
+}
 
 extern "C" size_t maxk_sspmm_backward_pull_workspace_size(int64_t num_rows, int64_t num_cols,
                                                           int32_t dim_origin, int32_t dim_k,

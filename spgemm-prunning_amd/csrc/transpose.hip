@@ -506,3 +506,236 @@ extern "C" int maxk_pull_plan(const int32_t *row_ptr, const int32_t *col_idx,
     MAXK_LAUNCHED("tile_ptr_kernel");
     return MAXK_OK;
 }
+
+// ---- stream plan (the stream pull backward, maxk_sspmm_backward_pull_stream) --------------
+// Columns cut into n_buckets buckets [bucket_col[b], bucket_col[b + 1]) of at most 2^cbits
+// columns (cbits = maxk_pull_shift(k)) that hold as nearly as possible the same number of
+// edges: boundary b is the column whose in-degree prefix sum is nearest b / n_buckets of the
+// edges, then clamped so that no bucket passes 2^cbits and the rest still cover the columns.
+// A stable radix sort of (bucket, row slice, edge id) lists every bucket's edges slice after
+// slice, CSR order inside a slice, which is CSR order throughout (maxk_pull_stream_slices); the
+// entry carries its global row.  ent = {row << cbits | column - bucket_col[b], weight}.
+namespace maxk {
+namespace {
+
+__global__ void stream_indeg_kernel(const int32_t *__restrict__ col_idx, int64_t num_e,
+                                    int num_cols, int32_t *__restrict__ indeg) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= num_e) return;
+    const int c = col_idx[e];
+    if (c >= 0 && c < num_cols) atomicAdd(&indeg[c], 1);
+}
+
+// One workgroup: every boundary's balanced column by binary search over the prefix sums
+// cpre[0 .. num_cols] (cpre[c] = edges into columns < c), then one thread clamps them in order.
+__global__ __launch_bounds__(1024) void stream_bounds_kernel(const int32_t *__restrict__ cpre,
+                                                             int num_cols, int nb, int cap,
+                                                             int32_t *__restrict__ bucket_col) {
+    const int64_t total = cpre[num_cols];
+    for (int i = threadIdx.x; i <= nb; i += blockDim.x) {
+        const int64_t want = total * i / nb;
+        int lo = 0, hi = num_cols;  // the first c with cpre[c] >= want
+        while (lo < hi) {
+            const int mid = (int)(((int64_t)lo + hi) >> 1);
+            if (cpre[mid] >= want) hi = mid; else lo = mid + 1;
+        }
+        if (lo > 0 && want - cpre[lo - 1] < cpre[lo] - want) --lo;  // the nearer of the two
+        bucket_col[i] = i == 0 ? 0 : i == nb ? num_cols : lo;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    int64_t prev = 0;
+    for (int i = 1; i < nb; ++i) {
+        int64_t lo = (int64_t)num_cols - (int64_t)(nb - i) * cap;  // the rest must still fit
+        lo = lo < prev ? prev : lo;
+        const int64_t hi = prev + cap < num_cols ? prev + cap : num_cols;
+        int64_t c = bucket_col[i];
+        c = c < lo ? lo : (c > hi ? hi : c);
+        bucket_col[i] = (int32_t)c;
+        prev = c;
+    }
+}
+
+// the bucket of column c: the last b with bucket_col[b] <= c (so bucket_col[b + 1] > c)
+__device__ __forceinline__ int stream_bucket_of(const int32_t *__restrict__ bucket_col, int nb,
+                                                int c) {
+    int lo = 0, hi = nb - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (bucket_col[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// one wave per row: key (bucket, slice) and source row of each of its edges
+__global__ void stream_key_kernel(const int32_t *__restrict__ row_ptr,
+                                  const int32_t *__restrict__ col_idx, int num_rows,
+                                  int num_cols, int rows_per_slice, int slices,
+                                  const int32_t *__restrict__ bucket_col, int nb,
+                                  int32_t *__restrict__ keys, int32_t *__restrict__ row_of) {
+    const int r = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave);
+    if (r >= num_rows) return;
+    const int lane = lane_id();
+    const int b = row_ptr[r], e = row_ptr[r + 1];
+    const int sl = r / rows_per_slice;
+    for (int i = b + lane; i < e; i += kWave) {
+        int c = col_idx[i];
+        c = c < 0 ? 0 : (c >= num_cols ? num_cols - 1 : c);  // out of range: stays in the plan
+        keys[i] = stream_bucket_of(bucket_col, nb, c) * slices + sl;
+        row_of[i] = r;
+    }
+}
+
+__global__ void stream_gather_kernel(const int32_t *__restrict__ eid,
+                                     const int32_t *__restrict__ sorted_keys,
+                                     const int32_t *__restrict__ row_of,
+                                     const int32_t *__restrict__ col_idx,
+                                     const float *__restrict__ edge_val, int64_t num_e, int cbits,
+                                     int slices, const int32_t *__restrict__ bucket_col,
+                                     uint2 *__restrict__ ent) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_e) return;
+    const int e = eid[i];
+    const uint32_t dst = (uint32_t)(col_idx[e] - bucket_col[sorted_keys[i] / slices]);
+    ent[i] = make_uint2(((uint32_t)row_of[e] << cbits) | (dst & ((1u << cbits) - 1u)),
+                        __float_as_uint(edge_val[e]));
+}
+
+// grp_ptr[b] = first slot whose bucket is >= b
+__global__ void stream_grp_ptr_kernel(const int32_t *__restrict__ sorted_keys, int64_t num_e,
+                                      int slices, int nb, int32_t *__restrict__ grp_ptr) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > num_e) return;
+    int cur = t < num_e ? sorted_keys[t] / slices : nb;
+    int prev = t == 0 ? -1 : sorted_keys[t - 1] / slices;
+    cur = cur > nb ? nb : cur;
+    prev = prev > nb ? nb : prev;
+    for (int x = prev + 1; x <= cur; ++x) grp_ptr[x] = (int32_t)t;
+}
+
+__global__ void stream_scale_kernel(const uint2 *__restrict__ ent, int64_t num_e, int cbits,
+                                    int64_t num_rows, const float *__restrict__ row_div,
+                                    uint2 *__restrict__ ent_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_e) return;
+    const uint2 v = ent[i];
+    const int64_t r = v.x >> cbits;
+    const float w = r < num_rows ? __uint_as_float(v.y) / row_div[r] : 0.0f;
+    ent_out[i] = make_uint2(v.x, __float_as_uint(w));
+}
+
+size_t stream_scan_bytes(int64_t n) {
+    size_t bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const int32_t *)nullptr,
+                                           (int32_t *)nullptr, (int)n);
+    return bytes;
+}
+
+}  // namespace
+}  // namespace maxk
+
+// The slices a stream plan sorts by.  A bucket's entries ordered by (row slice, CSR order) are
+// in CSR order whatever the slice count, since CSR order is row order: the count changes the
+// width of the sort key and nothing else (measured flat from 7 to 448), so 1.
+extern "C" int maxk_pull_stream_slices(int64_t, int64_t, int32_t, int32_t) { return 1; }
+
+extern "C" size_t maxk_pull_stream_plan_workspace_size(int64_t num_cols, int64_t num_e,
+                                                       int32_t n_buckets, int32_t slices) {
+    if (num_cols < 0 || num_e <= 0 || n_buckets <= 0 || slices <= 0) return 0;
+    const size_t sort = pull_sort_temp_bytes(num_e, (int64_t)n_buckets * slices);
+    const size_t scan = stream_scan_bytes(num_cols + 1);
+    return 5 * al256((size_t)num_e * 4) + 2 * al256((size_t)(num_cols + 1) * 4) +
+           al256(sort > scan ? sort : scan);
+}
+
+extern "C" int maxk_pull_stream_plan(const int32_t *row_ptr, const int32_t *col_idx,
+                                     const float *edge_val, int64_t num_rows, int64_t num_cols,
+                                     int64_t num_e, int32_t dim_k, int32_t n_buckets,
+                                     int32_t slices, int32_t *bucket_col, int32_t *grp_ptr,
+                                     uint32_t *ent, void *workspace, size_t workspace_bytes,
+                                     void *stream) {
+    clear_error();
+    MAXK_REQUIRE(num_rows >= 0 && num_rows < (1LL << 31), "num_rows out of range");
+    MAXK_REQUIRE(num_cols >= 1 && num_cols < (1LL << 31), "num_cols out of range");
+    MAXK_REQUIRE(num_e >= 0 && num_e < (1LL << 28), "num_e out of range");
+    const int cbits = maxk_pull_shift(dim_k);
+    MAXK_REQUIRE(dim_k > 0 && dim_k % 4 == 0 && cbits >= 4 && cbits <= 15,
+                 "stream plan needs dim_k %% 4 == 0, got %d", dim_k);
+    int row_bits = 0;
+    while ((1LL << row_bits) < num_rows) ++row_bits;
+    MAXK_REQUIRE(row_bits + cbits <= 32, "%d row bits + %d column bits exceed 32", row_bits, cbits);
+    MAXK_REQUIRE(n_buckets >= 1 && ((int64_t)n_buckets << cbits) >= num_cols,
+                 "%d buckets of 2^%d columns do not cover %lld columns", n_buckets, cbits,
+                 (long long)num_cols);
+    MAXK_REQUIRE(slices >= 1 && (int64_t)slices * n_buckets < (1LL << 31),
+                 "slices %d out of range", slices);
+    MAXK_REQUIRE(bucket_col && grp_ptr, "bucket_col/grp_ptr must not be NULL");
+    hipStream_t s = as_stream(stream);
+    const int nb = n_buckets;
+    if (num_e == 0 || num_rows == 0) {  // no entries: any widths that cover the columns
+        const size_t need = al256((size_t)(num_cols + 1) * 4);
+        MAXK_REQUIRE(workspace && workspace_bytes >= need, "workspace too small: need %zu", need);
+        int32_t *cpre = reinterpret_cast<int32_t *>(workspace);
+        if (int rc = zero_words(cpre, num_cols + 1, s)) return rc;
+        hipLaunchKernelGGL(stream_bounds_kernel, dim3(1), dim3(1024), 0, s, cpre, (int)num_cols,
+                           nb, 1 << cbits, bucket_col);
+        MAXK_LAUNCHED("stream_bounds_kernel");
+        return zero_words(grp_ptr, nb + 1, s);
+    }
+    MAXK_REQUIRE(row_ptr && col_idx && edge_val && ent, "CSR/plan pointers must not be NULL");
+    const size_t need = maxk_pull_stream_plan_workspace_size(num_cols, num_e, n_buckets, slices);
+    MAXK_REQUIRE(workspace && workspace_bytes >= need, "workspace too small: need %zu", need);
+    char *ws = reinterpret_cast<char *>(workspace);
+    const size_t a = al256((size_t)num_e * 4), c = al256((size_t)(num_cols + 1) * 4);
+    int32_t *keys = reinterpret_cast<int32_t *>(ws);
+    int32_t *keys_out = reinterpret_cast<int32_t *>(ws + a);
+    int32_t *ids = reinterpret_cast<int32_t *>(ws + 2 * a);
+    int32_t *eid = reinterpret_cast<int32_t *>(ws + 3 * a);
+    int32_t *row_of = reinterpret_cast<int32_t *>(ws + 4 * a);
+    int32_t *indeg = reinterpret_cast<int32_t *>(ws + 5 * a);
+    int32_t *cpre = reinterpret_cast<int32_t *>(ws + 5 * a + c);
+    void *tmp = ws + 5 * a + 2 * c;
+    size_t tmp_bytes = workspace_bytes - (5 * a + 2 * c);
+    const dim3 ge((unsigned)ceil_div(num_e, kBlock));
+    if (int rc = zero_words(indeg, num_cols + 1, s)) return rc;
+    hipLaunchKernelGGL(stream_indeg_kernel, ge, dim3(kBlock), 0, s, col_idx, num_e,
+                       (int)num_cols, indeg);
+    MAXK_LAUNCHED("stream_indeg_kernel");
+    MAXK_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, indeg, cpre, (int)(num_cols + 1), s));
+    hipLaunchKernelGGL(stream_bounds_kernel, dim3(1), dim3(1024), 0, s, cpre, (int)num_cols, nb,
+                       1 << cbits, bucket_col);
+    MAXK_LAUNCHED("stream_bounds_kernel");
+    const int rps = (int)((num_rows + slices - 1) / slices);
+    hipLaunchKernelGGL(stream_key_kernel, dim3((unsigned)ceil_div(num_rows * kWave, kBlock)),
+                       dim3(kBlock), 0, s, row_ptr, col_idx, (int)num_rows, (int)num_cols, rps,
+                       (int)slices, bucket_col, nb, keys, row_of);
+    MAXK_LAUNCHED("stream_key_kernel");
+    hipLaunchKernelGGL(iota_kernel, ge, dim3(kBlock), 0, s, ids, num_e);
+    MAXK_LAUNCHED("iota_kernel");
+    MAXK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_out, ids, eid,
+                                                (int)num_e, 0, key_bits((int64_t)nb * slices), s));
+    hipLaunchKernelGGL(stream_gather_kernel, ge, dim3(kBlock), 0, s, eid, keys_out, row_of,
+                       col_idx, edge_val, num_e, cbits, (int)slices, bucket_col,
+                       reinterpret_cast<uint2 *>(ent));
+    MAXK_LAUNCHED("stream_gather_kernel");
+    hipLaunchKernelGGL(stream_grp_ptr_kernel, dim3((unsigned)ceil_div(num_e + 1, kBlock)),
+                       dim3(kBlock), 0, s, keys_out, num_e, (int)slices, nb, grp_ptr);
+    MAXK_LAUNCHED("stream_grp_ptr_kernel");
+    return MAXK_OK;
+}
+
+extern "C" int maxk_pull_stream_entries_scale(const uint32_t *ent, int64_t num_e,
+                                              int64_t num_rows, int32_t dim_k,
+                                              const float *row_div, uint32_t *ent_out,
+                                              void *stream) {
+    clear_error();
+    const int cbits = maxk_pull_shift(dim_k);
+    MAXK_REQUIRE(num_e >= 0 && num_rows >= 0 && cbits >= 4, "sizes out of range");
+    if (num_e == 0) return MAXK_OK;
+    MAXK_REQUIRE(ent && row_div && ent_out, "pointers must not be NULL");
+    hipLaunchKernelGGL(stream_scale_kernel, dim3((unsigned)ceil_div(num_e, kBlock)), dim3(kBlock),
+                       0, as_stream(stream), reinterpret_cast<const uint2 *>(ent), num_e, cbits,
+                       num_rows, row_div, reinterpret_cast<uint2 *>(ent_out));
+    MAXK_LAUNCHED("stream_scale_kernel");
+    return MAXK_OK;
+}

@@ -24,7 +24,7 @@ import contextlib
 import ctypes
 import os
 import warnings
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -57,6 +57,7 @@ __all__ = [
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
+    "pull_stream_plan", "pull_stream_buckets", "PullStreamPlan",
 ]
 
 FULL_DIM = 256  # the reference binding's fixed output width (cuda_kernel_bindings.cpp:70)
@@ -1161,6 +1162,92 @@ def pull_plan(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
     return _PULL_CACHE.get((indptr, indices, values), (shift, S, int(num_cols)), build, cache)
 
 
+_STREAM_CACHE = TensorCache()
+
+
+class PullStreamPlan(NamedTuple):
+    """Plan of the stream pull backward (pull_stream_plan); opaque to callers, who pass it back
+    as `plan=`."""
+    bucket_col: torch.Tensor  # int32 [n_buckets + 1]
+    grp_ptr: torch.Tensor     # int32 [n_buckets + 1]
+    ent: torch.Tensor         # int32 [E, 2]
+    shift: int                # column bits of an entry: maxk_pull_shift(k)
+    n_buckets: int
+    slices: int
+
+
+def _stream_on() -> bool:
+    """MAXK_PULL_STREAM=0 keeps the tiled pull everywhere (the same build, both ways)."""
+    return os.environ.get("MAXK_PULL_STREAM", "1") != "0"
+
+
+def pull_stream_buckets(dev, num_rows: int, num_cols: int, num_e: int, dim: int, k: int) -> int:
+    """Buckets of the stream pull backward for this shape on `dev` (maxk_pull_stream_buckets
+    with that device's CU count), or 0 where the tiled pull stays: see include/maxk_hip.h."""
+    if not _stream_on():
+        return 0
+    return _sized(dev, "maxk_pull_stream_buckets", int(num_rows), int(num_cols), int(num_e),
+                  int(dim), int(k), 0)
+
+
+def pull_stream_plan(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
+                     num_cols: int, k: int, dim: int = 256, groups: Optional[int] = None,
+                     slices: Optional[int] = None, cache: bool = True) -> PullStreamPlan:
+    """The stream pull backward's plan of a CSR graph and its edge values at width k
+    (maxk_pull_stream_plan): `groups` buckets of at most 2^maxk_pull_shift(k) columns holding
+    about equal edge counts (default pull_stream_buckets: whole rounds of one workgroup per CU
+    and part; an error where that rule refuses the shape), each bucket's edges ordered by
+    (one of `slices` row slices, CSR order) as {row << shift | column in the bucket, weight
+    bits}.  `slices` (default maxk_pull_stream_slices: 1) only widens the sort key: a bucket's
+    entries are in CSR order whatever it is.  Built on the GPU, cached like pull_plan."""
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (values, "values", torch.float32)):
+        _need(t, n, dt)
+    L = _lib()
+    dev = indices.device
+    num_rows, E = indptr.numel() - 1, indices.numel()
+    shift = int(L.maxk_pull_shift(int(k)))
+    if k % 4 or shift < 4:
+        raise RuntimeError(f"pull_stream_plan needs k % 4 == 0, got k={k}")
+    nb = int(groups) if groups else pull_stream_buckets(dev, num_rows, num_cols, E, dim, k)
+    if nb <= 0:
+        raise RuntimeError(f"pull_stream_plan: the stream path does not apply to {num_rows} x "
+                           f"{num_cols}, dim={dim}, k={k}; pass groups= or use pull_plan")
+    S = int(slices) if slices else int(L.maxk_pull_stream_slices(num_rows, int(num_cols),
+                                                                 int(dim), int(k)))
+
+    def build():
+        bcol = torch.empty(nb + 1, dtype=torch.int32, device=dev)
+        gptr = torch.empty(nb + 1, dtype=torch.int32, device=dev)
+        ent = torch.empty(max(E, 1), 2, dtype=torch.int32, device=dev)[:E]
+        _launch_ws(dev, "maxk_pull_stream_plan", "maxk_pull_stream_plan_workspace_size",
+                   (max(int(num_cols), 1), max(E, 1), nb, S),
+                   (_ptr(indptr), _ptr(indices), _ptr(values), num_rows, int(num_cols), E, int(k),
+                    nb, S, _ptr(bcol), _ptr(gptr), _ptr(ent)))
+        return PullStreamPlan(bcol, gptr, ent, shift, nb, S)
+    return _STREAM_CACHE.get((indptr, indices, values), (int(k), nb, S, int(num_cols)), build,
+                             cache)
+
+
+def _scaled_stream_entries(plan: PullStreamPlan, num_rows: int, k: int,
+                           row_div: torch.Tensor) -> Optional[torch.Tensor]:
+    """_scaled_entries for a stream plan (maxk_pull_stream_entries_scale): the row is in the
+    entry, so one pass over the entries."""
+    ent = plan.ent
+    sc = _SCALED.lookup((ent, row_div), ())
+    if sc is not None:
+        return sc
+    if ent.is_cuda and torch.cuda.is_current_stream_capturing():
+        return None  # as _scaled_entries: nothing is built inside a capture
+
+    def build():
+        sc = torch.empty_like(ent)
+        _launch(ent.device, "maxk_pull_stream_entries_scale", _ptr(ent), ent.shape[0], num_rows,
+                int(k), _ptr(row_div), _ptr(sc), _stream(ent.device))
+        return sc
+    return _SCALED.get((ent, row_div), (), build)
+
+
 _HYBRID_CACHE = TensorCache()
 MAXK_PULL_NO_REDUCE, MAXK_PULL_REDUCE_ONLY = 2, 4  # include/maxk_hip.h
 MAXK_HYBRID_PRESCALED = 1
@@ -1388,7 +1475,7 @@ def backward_plan(indices: torch.Tensor, num_cols: int, k: int, mode: Optional[s
             raise RuntimeError(f"backward_plan: mode '{mode}' needs indptr= and values=")
         if mode == "hybrid":
             return hybrid_plan(indptr, indices, values, num_cols, k, dim or 256)
-        return pull_plan(indptr, indices, values, num_cols, k, dim or 256)
+        return _pull_plan_for(indptr, indices, values, num_cols, k, dim or 256)
     if mode == "dense":
         if indptr is None or values is None:
             raise RuntimeError("backward_plan: mode 'dense' needs indptr= and values=")
@@ -1424,7 +1511,11 @@ def sspmm_backward(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Te
     row_div the plan's weights are pre-divided, once per divisor: _scaled_entries);
     uses the graph's pull plan (built once per (indptr, indices, values) and cached, or
     `plan=` from pull_plan()); fp64 tile sums, so two runs agree except in rare rounding
-    ties (use "csc" for bitwise repeatability).
+    ties (use "csc" for bitwise repeatability).  Where pull_stream_buckets accepts the shape
+    (k % 4 == 0, buckets that fill whole rounds of one workgroup per CU without narrowing
+    them by more than 12.5 %; MAXK_PULL_STREAM=0 turns it off) the stream path runs instead:
+    one workgroup per (bucket, part) walks all of the bucket's entries and stores its rows
+    itself, no tile partials and no reduce (pull_stream_plan(), or that plan as `plan=`).
     mode "csc": two-phase, atomic-free and bitwise deterministic, using the graph's
     transpose plan (built once and cached, or `plan=` from transpose_plan()).
     mode "bsort" (k % 4 == 0): two-phase, phase 1 writing each window of maxk_bsort_window(k)
@@ -1538,10 +1629,33 @@ def _bwd_hybrid(indptr, indices, values, G, row_div, sel, edge_sel, out, shape, 
     # it read (ws included) is free for reuse in that stream's order
 
 
+def _pull_plan_for(indptr, indices, values, num_cols, k, dim):
+    """The plan mode "pull" uses for a graph: the stream plan where pull_stream_buckets accepts
+    the shape on the graph's device, else the tiled pull_plan."""
+    num_rows, E = indptr.numel() - 1, indices.numel()
+    if k % 4 == 0 and pull_stream_buckets(indices.device, num_rows, num_cols, E, dim, k) > 0:
+        return pull_stream_plan(indptr, indices, values, num_cols, k, dim)
+    return pull_plan(indptr, indices, values, num_cols, k, dim)
+
+
 def _bwd_pull(indptr, indices, values, G, row_div, sel, edge_sel, out, shape, chunk, plan):
     num_rows, num_cols, E, D, k = shape
-    tptr, ent, shift, S = (plan if plan is not None else
-                           pull_plan(indptr, indices, values, num_cols, k, D))
+    if plan is None:
+        plan = _pull_plan_for(indptr, indices, values, num_cols, k, D)
+    if isinstance(plan, PullStreamPlan):
+        ent = plan.ent
+        if plan.shift != int(_lib().maxk_pull_shift(int(k))) or ent.shape[0] != E:
+            raise RuntimeError(f"the stream plan was not built for this graph at k={k}")
+        if row_div is not None and E > 0 and _prescale():
+            sc = _scaled_stream_entries(plan, num_rows, k, row_div)
+            if sc is not None:
+                ent, row_div = sc, None
+        _launch_ws(G.device, "maxk_sspmm_backward_pull_stream",
+                   "maxk_sspmm_backward_pull_stream_workspace_size", (num_rows, num_cols, D, k),
+                   (_ptr(G), _ptr(row_div), _ptr(sel), _ptr(plan.bucket_col), _ptr(plan.grp_ptr),
+                    _ptr(ent), plan.n_buckets, _ptr(out), *shape))
+        return
+    tptr, ent, shift, S = plan
     if row_div is not None and E > 0 and _prescale():
         sc = _scaled_entries(ent, None, tptr, num_rows, num_cols, shift, S, row_div)
         if sc is not None:

@@ -158,6 +158,15 @@ SIGNATURES = {
     "maxk_pull_plan_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32]),
     "maxk_pull_plan": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _sz,
                                       _p]),
+    "maxk_pull_stream_buckets": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32]),
+    "maxk_pull_stream_slices": (ctypes.c_int, [_i64, _i64, _i32, _i32]),
+    "maxk_pull_stream_plan_workspace_size": (_sz, [_i64, _i64, _i32, _i32]),
+    "maxk_pull_stream_plan": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _p,
+                                             _p, _p, _p, _sz, _p]),
+    "maxk_pull_stream_entries_scale": (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _p]),
+    "maxk_sspmm_backward_pull_stream_workspace_size": (_sz, [_i64, _i64, _i32, _i32]),
+    "maxk_sspmm_backward_pull_stream": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i32, _p, _i64,
+                                                       _i64, _i64, _i32, _i32, _p, _sz, _p]),
     "maxk_backward_mode_auto": (ctypes.c_int, [_i64, _i64, _i64, _i32, _i32, ctypes.c_double]),
     "maxk_pull_locality": (ctypes.c_int, [_p, _p, _i64, _i64, _i32,
                                           ctypes.POINTER(ctypes.c_double), _p, _sz, _p]),
