@@ -739,6 +739,61 @@ int maxk_dot_attention_heads_backward(
     size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Attention dropout inside the fused dot-product attention: the mask of the attention-dropout
+ * block above (head h of edge e is dropped iff word h & 3 of Philox4x32-10(counter
+ * (e, 0, h >> 2, 0), key (seed lo, seed hi)) is < thr; d_he = dropped ? 0 : scale), word for word:
+ * maxk_edge_dropout_heads and both entries below agree on it whatever chunk_edges, the work-item
+ * cut, num_heads or the padded head count are, and seed travels by value (a captured graph
+ * replays the same mask).  0 <= p < 1 and not NaN, otherwise MAXK_ERR_INVALID naming p, before
+ * any launch.
+ * maxk_dot_attention_heads_dropout: maxk_dot_attention_heads with
+ *   out[h, r, cbsr_idx[c,l]] += alpha[h,e] * d_he * cbsr_val[c,l].
+ *   row_max and row_sum are the statistics of the undropped softmax, bitwise those of
+ *   maxk_dot_attention_heads at the same chunk_edges: dropout follows the normalisation.  The
+ *   first sweep is unchanged; in the second the sum of p takes the unmasked p, the kernel sums
+ *   p * (0 or 1) * value and multiplies the row by scale once, after the division by z (a hub
+ *   row: in the merge of its pieces).  One Philox evaluation serves a quad of heads and several
+ *   wave steps.
+ * maxk_dot_attention_heads_dropout_backward: maxk_dot_attention_heads_backward with
+ *   gl_he = alpha_he * (d_he * ga_he - t_hr),
+ *   grad_cbsr[c,l] = sum_h sum_{e -> c} (alpha_he * d_he * grad_out[h,r,s] + scale * gl_he * q[h,r,s]),
+ *   grad_q and t_hr as there, t from the dropped out: sum_e alpha_he * d_he * ga_he is still the
+ *   dot product of out[h,r,:] and grad_out[h,r,:], so a cut row is still walked once.  Same p and
+ *   seed as the forward that produced out.
+ * maxk_dot_edge_alpha_heads has no masked form: a rebuilt backward masks its result (for the
+ *   aggregation's coefficients) and grad_alpha with maxk_edge_dropout_heads.
+ * Both take the arguments, shapes, writes, workspace (the _workspace_size queries return the
+ *   sizes of the entries without dropout), memory contract, argument errors and repeatability of
+ *   the entries they extend; p == 0 runs those entries' kernels and is bitwise equal to them.
+ * Numerics (tests/dot_attn_dropout_ref.py): the bounds of the entries without dropout carried
+ *   through the factor d <= scale, plus one rounding (u = 2^-24, relative) for the product by
+ *   scale.  Non-finite values follow the IEEE evaluation of the formulas with d as a factor:
+ *   0 * NaN and 0 * Inf are NaN, dropping does not shield.  For finite inputs a row all of whose
+ *   edges are dropped in head h has exact zeros in out[h, r, :].
+ * No global and no LDS atomics.
+ * ------------------------------------------------------------------------- */
+size_t maxk_dot_attention_heads_dropout_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                       int64_t num_e, int32_t dim_origin,
+                                                       int32_t dim_k, int32_t num_heads,
+                                                       int32_t chunk_edges);
+int maxk_dot_attention_heads_dropout(
+    const int32_t *row_ptr, const int32_t *col_idx, const float *q, float scale,
+    const float *cbsr_val, const uint8_t *cbsr_idx, float *out, float *row_max, float *row_sum,
+    int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+    int32_t num_heads, int32_t chunk_edges, float p, uint64_t seed, void *workspace,
+    size_t workspace_bytes, void *stream);
+size_t maxk_dot_attention_heads_dropout_backward_workspace_size(
+    int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+    int32_t num_heads, int32_t chunk_edges);
+int maxk_dot_attention_heads_dropout_backward(
+    const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr, const int32_t *csc_eid,
+    const float *q, float scale, const float *cbsr_val, const uint8_t *cbsr_idx, const float *out,
+    const float *row_max, const float *row_sum, const float *grad_out, float *grad_q,
+    float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+    int32_t dim_k, int32_t num_heads, int32_t chunk_edges, float p, uint64_t seed,
+    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Backward outer-product sampled SpMM (SSpMM):
  *   grad_cbsr[c,l] = sum_{e=(r->c)} edge_val[e] * grad_out[r, cbsr_idx[c,l]] / row_div[r]
  *                  = (A^T diag(1/row_div) G)[c, cbsr_idx[c,l]]     (from the CSR of A)

@@ -9,7 +9,8 @@
 // e is the edge's CSR position.  Nothing else enters: not chunk_edges, not the work-item cut, not
 // num_heads or the padded head count, not which kernel asks.  One evaluation serves the four
 // heads of a quad (drop_bits).  Included by every kernel that masks: attn_dropout.hip (the
-// elementwise entry), gat_attention_heads.hip and gat_attention_heads_bwd.hip.
+// elementwise entry), gat_attention_heads.hip, gat_attention_heads_bwd.hip,
+// dot_attention_heads.hip and dot_attention_heads_bwd.hip.
 #pragma once
 #include <cmath>
 #include <cstdint>

@@ -42,11 +42,20 @@
 // No global atomics, no LDS atomics; every sum has an order fixed by (graph, chunk, k, H), so the
 // result is bitwise repeatable, and head h's slice is computed from head h's query only.
 // LDS per wave: (H + G) * DS floats (16.6 KB at H = 8, G = 8, D = 256; 12.5 KB at k = 16).
+// maxk_dot_attention_heads_dropout is the same walk with the attention-dropout mask of
+// attn_dropout.h multiplied in (the DROP instantiations): out sums alpha * d * value, the
+// statistics stay those of the undropped softmax, p == 0 launches the kernels without a mask.
 #include <cmath>
 
+#include "attn_dropout.h"
 #include "dot_logit.h"
 #include "edge_softmax.h"
 #include "heads_walk.h"
+
+// Waves per SIMD the masked forward is compiled for (1: whatever its registers allow).
+#ifndef MAXK_DATH_DROP_WAVES
+#define MAXK_DATH_DROP_WAVES 4
+#endif
 
 namespace maxk {
 namespace {
@@ -108,21 +117,57 @@ __device__ __forceinline__ void piece_max(const float *qrow, const int32_t *__re
 // head's logit against qh; returns the lane's sum of p (the same in every lane of a group).
 // active: the group has an edge slot and a head in this pass; else it writes its trash column
 // only.  POISON: p = NaN and nothing is summed (the rows whose z is no positive number).
-template <int KG, int U, bool POISON>
+// DROP (attn_dropout.h), the scheme of gat_attention_heads.hip's walk_attn: a wave step holds
+// EP * U edges and the pass's heads lie in dp.qp <= 2 quads, so one Philox evaluation per lane --
+// lane t on the edge at offset t % span of the next S = 64 / (EP * U * qp) steps (span =
+// S * EP * U; its CSR position is sb + its index in the piece) and the quad dp.q0 + t / span --
+// serves S steps: four ballots, one per head of a quad, carry the bits, and each group keeps its
+// head's 64 (`mine`).  The sum of p takes the unmasked weights and the products p * (0 or 1): a
+// dropped NaN or Inf stays NaN.
+struct DropPass {
+    int q0, qp, head;  // the pass's first quad of heads and their number; the group's head
+};
+template <int KG, int U, bool POISON, bool DROP>
 __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
                                           const int32_t *__restrict__ col_idx, float shift,
                                           const uint8_t *__restrict__ rec, int RS, int sb, int se,
-                                          int k, int trash, int EP, int eg, bool active, int lane) {
+                                          int k, int trash, int EP, int eg, bool active, int lane,
+                                          const MaskArg<DROP> &dm, const DropPass &dp) {
+    static_assert(!(POISON && DROP), "the NaN walk has no mask");
     const int l0 = lane % KG;
     const int n = se - sb;  // wave-uniform, <= 2 * chunk
     const auto crs = wave_buffer(col_idx + sb, (uint32_t)n * 4u);
     const auto rrs = wave_buffer(rec, 0xffffffffu);
     float ps = 0.f;
+    const int EU = EP * U;
+    int S = 1, span_log = 0, js = 0, qsel = 0;
+    uint64_t mine = 0;
+    if constexpr (DROP) {
+        S = kWave / (EU * dp.qp);  // powers of two, EU * qp <= 64
+        span_log = 31 - __clz(S * EU);
+        qsel = min(max((dp.head >> 2) - dp.q0, 0), dp.qp - 1);
+    }
     for (int base = 0; base < n; base += EP * U) {
         int c[U];
 #pragma unroll
         for (int u = 0; u < U; ++u)
             c[u] = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, (base + u * EP + eg) * 4, 0, 0);
+        float keep[DROP ? U : 1];  // DROP: 0 where the group's head of slot u is dropped, else 1
+        if constexpr (DROP) {
+            if (js == 0) {  // wave-uniform: the masks of this and the next S - 1 steps
+                const uint32_t bits =
+                    drop_bits(dm, (uint32_t)(sb + base + (lane & ((1 << span_log) - 1))),
+                              (uint32_t)(dp.q0 + (lane >> span_log)));
+                const uint64_t b0 = __ballot(bits & 1u), b1 = __ballot(bits & 2u),
+                               b2 = __ballot(bits & 4u), b3 = __ballot(bits & 8u);
+                const int hb = dp.head & 3;
+                mine = (hb == 0 ? b0 : hb == 1 ? b1 : hb == 2 ? b2 : b3) >> (qsel << span_log);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                keep[u] = (mine >> (js * EU + u * EP + eg)) & 1 ? 0.f : 1.f;
+            js = js + 1 == S ? 0 : js + 1;
+        }
         if (k <= KG) {  // the slot's value and selector serve the logit and the product
             const bool lok = l0 < k;
             const uint32_t lc = (uint32_t)(lok ? l0 : k - 1);
@@ -141,6 +186,7 @@ __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
                     const float l = logit_sum<KG>(logit_term(v[u], s[u], qh, trash, lok, 0.f));
                     p = live ? expf(l - shift) : 0.f;
                     ps += p;
+                    if constexpr (DROP) p *= keep[u];
                 }
                 float *a = &acc_g[live && lok ? min(s[u], trash) : trash];
                 *a = __builtin_fmaf(p, v[u], *a);
@@ -157,6 +203,7 @@ __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
                 for (int u = 0; u < U; ++u) {
                     p[u] = active && base + u * EP + eg < n ? expf(l[u] - shift) : 0.f;
                     ps += p[u];
+                    if constexpr (DROP) p[u] *= keep[u];
                 }
             }
             scatter_records<KG, U>(acc_g, rrs, RS, k, trash, l0, c, p, active, base, EP, eg, n);
@@ -165,14 +212,18 @@ __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
     return ps;
 }
 
-template <int KG, int U>
-__global__ __launch_bounds__(kBlock) void dath_fwd_kernel(
+// DROP: held to the four waves per SIMD of the kernel without a mask (128 VGPRs); the Philox
+// rounds then spill 28 bytes per lane (84 at KG = 32) around the once-in-S-steps evaluation
+// instead of taking 142 to 151 VGPRs and three waves (MAXK_DATH_DROP_WAVES=1;
+// profiles/r22/dot_attn_dropout/).
+template <int KG, int U, bool DROP>
+__global__ __launch_bounds__(kBlock, DROP ? MAXK_DATH_DROP_WAVES : 1) void dath_fwd_kernel(
     const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
     const float *__restrict__ q, float scale, const uint8_t *__restrict__ rec, int RS,
     float *__restrict__ out, float *__restrict__ row_max, float *__restrict__ row_sum,
     float *__restrict__ slab, float *__restrict__ slab_m, float *__restrict__ slab_z,
     int32_t *__restrict__ slab_row, int num_rows, int64_t num_e, int D, int DS, int k, int chunk,
-    int n_items, int H, int HC, int flags) {
+    int n_items, int H, int HC, int flags, MaskArg<DROP> dm) {
     // flags: store_flags (heads_walk.h), and bit 2 16-B query loads (D % 4 == 0, q 16-B aligned)
     constexpr int G = kWave / KG;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -215,20 +266,25 @@ __global__ __launch_bounds__(kBlock) void dath_fwd_kernel(
             float ps = 0.f;
             wave_lds_fence();
             if (n > 0)
-                ps = walk_dot<KG, U, false>(g.acc_g, qh, col_idx, shift_of(mh), rec, RS, (int)sb,
-                                            (int)se, k, DS - 1, g.EP, g.eg, active, lane);
+                ps = walk_dot<KG, U, false, DROP>(
+                    g.acc_g, qh, col_idx, shift_of(mh), rec, RS, (int)sb, (int)se, k, DS - 1, g.EP,
+                    g.eg, active, lane, dm,
+                    DropPass{h0 >> 2, ((min(h0 + HC, H) - 1) >> 2) - (h0 >> 2) + 1, head});
             const int bad = bad_heads<KG>(ps, g.EP, HC, h0, H);
             if (whole && n > 0 && bad) {  // rare: NaN wherever such a head's row has an addend
                 wave_lds_fence();
-                walk_dot<KG, U, true>(g.acc_g, qh, col_idx, 0.f, rec, RS, (int)sb, (int)se, k,
-                                      DS - 1, g.EP, g.eg, active && ((bad >> g.hh) & 1), lane);
+                walk_dot<KG, U, true, false>(g.acc_g, qh, col_idx, 0.f, rec, RS, (int)sb, (int)se,
+                                             k, DS - 1, g.EP, g.eg, active && ((bad >> g.hh) & 1),
+                                             lane, NoMask{}, DropPass{0, 1, 0});
             }
             wave_lds_fence();
             for (int j = 0; j < HC && h0 + j < H; ++j) {
                 const float zj = pass_z<KG>(ps, j, g.EP, HC);
                 const bool ok = !((bad >> j) & 1);
-                flush_head<false>(acc + j * DS, g.EP, HC * DS, dst + (int64_t)(h0 + j) * hstride,
-                                  D, zj, whole && ok, vec, nt && to_out, lane, 1.f);
+                float mul = 1.f;
+                if constexpr (DROP) mul = dm.scale;
+                flush_head<DROP>(acc + j * DS, g.EP, HC * DS, dst + (int64_t)(h0 + j) * hstride, D,
+                                 zj, whole && ok, vec, nt && to_out, lane, mul);
                 // the head's maximum sits in the lanes of group j (edge slot 0, head h0 + j)
                 const float mj = uniform(__shfl(mh, j * KG));
                 if (lane == 0) {
@@ -400,14 +456,41 @@ extern "C" size_t maxk_dot_attention_heads_workspace_size(int64_t num_rows, int6
         .total;
 }
 
-extern "C" int maxk_dot_attention_heads(const int32_t *row_ptr, const int32_t *col_idx,
-                                        const float *q, float scale, const float *cbsr_val,
-                                        const uint8_t *cbsr_idx, float *out, float *row_max,
-                                        float *row_sum, int64_t num_rows, int64_t num_cols,
-                                        int64_t num_e, int32_t dim_origin, int32_t dim_k,
-                                        int32_t num_heads, int32_t chunk_edges, void *workspace,
-                                        size_t workspace_bytes, void *stream) {
-    clear_error();
+namespace {
+// The walk and the fix-up of both forward entries, with or without a mask.
+template <bool DROP>
+int launch_dot_fwd(const int32_t *row_ptr, const int32_t *col_idx, const float *q, float scale,
+                   const uint8_t *rec, float *out, float *row_max, float *row_sum, float *slab,
+                   float *slab_m, float *slab_z, int32_t *slab_row, int64_t num_rows,
+                   int64_t num_e, int D, int k, int H, const DotLayout &L, hipStream_t s,
+                   const MaskArg<DROP> &dm) {
+    const RecordGeom &R = L.R;
+    constexpr int U = MAXK_FWD_U;
+    const int flags =
+        store_flags(out, H, num_rows, D) | (D % 4 == 0 && ((uintptr_t)q & 15) == 0 ? 4 : 0);
+    const bool ok = with_const<8, 16, 32, 64>(R.kg, [&](auto kg_c) {
+        constexpr int KG = decltype(kg_c)::value;
+        hipLaunchKernelGGL((dath_fwd_kernel<KG, U, DROP>), item_grid(L.n_items), dim3(kBlock),
+                           L.lds, s, row_ptr, col_idx, q, scale, rec, R.RS, out, row_max, row_sum,
+                           slab, slab_m, slab_z, slab_row, (int)num_rows, num_e, D, R.DS, k,
+                           L.chunk, L.n_items, H, L.hc, flags, dm);
+    });
+    if (!ok) return bad_lanes(R.kg);
+    MAXK_LAUNCHED("dath_fwd_kernel");
+    float mul = 1.f;
+    if constexpr (DROP) mul = dm.scale;
+    return launch_softmax_fixup<DROP>(row_ptr, col_idx, rec, R.RS, k, slab, slab_m, slab_z,
+                                      slab_row, out, row_max, row_sum, num_rows, D, L.n_items, H,
+                                      mul, s);
+}
+
+// Both forward entries; dm: the dropout entry's mask, null for none.
+int dot_attention_heads(const int32_t *row_ptr, const int32_t *col_idx, const float *q,
+                        float scale, const float *cbsr_val, const uint8_t *cbsr_idx, float *out,
+                        float *row_max, float *row_sum, int64_t num_rows, int64_t num_cols,
+                        int64_t num_e, int32_t dim_origin, int32_t dim_k, int32_t num_heads,
+                        int32_t chunk_edges, void *workspace, size_t workspace_bytes,
+                        void *stream, const DropMask *dm) {
     if (int rc = check_dot(num_rows, num_cols, num_e, scale, dim_origin, dim_k, num_heads,
                            chunk_edges))
         return rc;
@@ -438,21 +521,49 @@ extern "C" int maxk_dot_attention_heads(const int32_t *row_ptr, const int32_t *c
     int32_t *slab_row = reinterpret_cast<int32_t *>(ws + L.S.row_off);
     if (int rc = launch_cbsr_pack(cbsr_val, cbsr_idx, rec, num_cols, k, R.RS, D, R.DS - 1, s))
         return rc;
-    constexpr int U = MAXK_FWD_U;
-    const int flags =
-        store_flags(out, H, num_rows, D) | (D % 4 == 0 && ((uintptr_t)q & 15) == 0 ? 4 : 0);
-    const bool ok = with_const<8, 16, 32, 64>(R.kg, [&](auto kg_c) {
-        constexpr int KG = decltype(kg_c)::value;
-        hipLaunchKernelGGL((dath_fwd_kernel<KG, U>), item_grid(L.n_items), dim3(kBlock), L.lds, s,
-                           row_ptr, col_idx, q, scale, rec, R.RS, out, row_max, row_sum, slab,
-                           slab_m, slab_z, slab_row, (int)num_rows, num_e, D, R.DS, k, L.chunk,
-                           L.n_items, H, L.hc, flags);
-    });
-    if (!ok) return bad_lanes(R.kg);
-    MAXK_LAUNCHED("dath_fwd_kernel");
-    return launch_softmax_fixup<false>(row_ptr, col_idx, rec, R.RS, k, slab, slab_m, slab_z,
-                                       slab_row, out, row_max, row_sum, num_rows, D, L.n_items, H,
-                                       1.f, s);
+    if (dm)
+        return launch_dot_fwd<true>(row_ptr, col_idx, q, scale, rec, out, row_max, row_sum, slab,
+                                    slab_m, slab_z, slab_row, num_rows, num_e, D, k, H, L, s, *dm);
+    return launch_dot_fwd<false>(row_ptr, col_idx, q, scale, rec, out, row_max, row_sum, slab,
+                                 slab_m, slab_z, slab_row, num_rows, num_e, D, k, H, L, s,
+                                 NoMask{});
+}
+}  // namespace
+
+extern "C" int maxk_dot_attention_heads(const int32_t *row_ptr, const int32_t *col_idx,
+                                        const float *q, float scale, const float *cbsr_val,
+                                        const uint8_t *cbsr_idx, float *out, float *row_max,
+                                        float *row_sum, int64_t num_rows, int64_t num_cols,
+                                        int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                                        int32_t num_heads, int32_t chunk_edges, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+    clear_error();
+    return dot_attention_heads(row_ptr, col_idx, q, scale, cbsr_val, cbsr_idx, out, row_max,
+                               row_sum, num_rows, num_cols, num_e, dim_origin, dim_k, num_heads,
+                               chunk_edges, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" size_t maxk_dot_attention_heads_dropout_workspace_size(
+    int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+    int32_t num_heads, int32_t chunk_edges) {
+    return maxk_dot_attention_heads_workspace_size(num_rows, num_cols, num_e, dim_origin, dim_k,
+                                                   num_heads, chunk_edges);
+}
+
+extern "C" int maxk_dot_attention_heads_dropout(
+    const int32_t *row_ptr, const int32_t *col_idx, const float *q, float scale,
+    const float *cbsr_val, const uint8_t *cbsr_idx, float *out, float *row_max, float *row_sum,
+    int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+    int32_t num_heads, int32_t chunk_edges, float p, uint64_t seed, void *workspace,
+    size_t workspace_bytes, void *stream) {
+    clear_error();
+    if (int rc = check_dropout(p)) return rc;
+    // p == 0 drops nothing and scales by 1: the kernels of the entry without dropout
+    const DropMask dm = drop_mask(p, seed);
+    return dot_attention_heads(row_ptr, col_idx, q, scale, cbsr_val, cbsr_idx, out, row_max,
+                               row_sum, num_rows, num_cols, num_e, dim_origin, dim_k, num_heads,
+                               chunk_edges, workspace, workspace_bytes, stream,
+                               p > 0.f ? &dm : nullptr);
 }
 
 extern "C" size_t maxk_dot_edge_alpha_heads_workspace_size(int64_t num_rows, int64_t num_cols,

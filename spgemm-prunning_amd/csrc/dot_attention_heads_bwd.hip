@@ -44,8 +44,13 @@
 // No global atomics, no LDS atomics; every sum has an order fixed by (graph, chunk, k, H).  Head
 // h's slice of grad_q is computed from head h's q, statistics, out and grad_out alone.
 // LDS per wave: walk A 2 * H * DS floats (16.6 KB at H = 8, D = 256: 8 waves per CU), B G * DS.
+// maxk_dot_attention_heads_dropout_backward is the same sequence with the attention-dropout mask
+// of attn_dropout.h in walk A (the DROP instantiations): gl = alpha * (d * ga - t) and
+// T = sum_h (alpha * d * g + gl * sq), t from the dropped out; B, glT and the CSC sum are
+// unchanged; p == 0 launches the kernels without a mask.
 #include <cmath>
 
+#include "attn_dropout.h"
 #include "dot_logit.h"
 #include "edge_softmax.h"
 #include "heads_walk.h"
@@ -91,14 +96,19 @@ struct HeadLane {
 };
 
 // The edges [sb, se) (sb < se) of one row whose grad_out rows are staged in grow and whose scaled
-// query rows are staged in qrow: stores their T rows and glT vectors.
-template <int KG, int HP, int U>
+// query rows are staged in qrow: stores their T rows and glT vectors.  DROP (attn_dropout.h), as
+// gat_attention_heads_bwd.hip's walk: lane j < U * QP of a group evaluates the mask of the
+// group's edge j % U for the quad of heads j / U, QP = ceil(HP / 4) quads; lane h fetches its
+// head's bit with one shuffle per edge and keeps alpha * d beside alpha: T gains alpha * d * g
+// and gl = alpha * (d * ga - t), t from the dropped out.
+template <int KG, int HP, int U, bool DROP>
 __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *qrow, int DS,
                                                const int32_t *__restrict__ col_idx,
                                                const uint8_t *__restrict__ rec, int RS,
                                                float *__restrict__ T, float *__restrict__ glT,
                                                int H, int D, int sb, int se, int k,
-                                               const HeadLane &hd, int lane) {
+                                               const HeadLane &hd, int lane,
+                                               const MaskArg<DROP> &dm) {
     constexpr int G = kWave / KG;
     const int grp = lane / KG, l0 = lane % KG;
     const int lane0 = lane - l0;  // the group's first lane
@@ -118,7 +128,20 @@ __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *q
         float lg[U], ga[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) lg[u] = ga[u] = 0.f;
-        // lane h: alpha and gl from them
+        uint32_t gone = 0u;  // DROP, lane h: bit u, head h of the group's edge u is dropped
+        if constexpr (DROP) {
+            constexpr int QP = (HP + 3) / 4;
+            static_assert(U * QP <= KG, "a group evaluates its step's masks in one round");
+            const uint32_t bits = drop_bits(
+                dm, (uint32_t)(sb + base + (l0 % U) * G + grp), (uint32_t)((l0 / U) % QP));
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t b = __shfl(bits, lane0 + ((l0 >> 2) % QP) * U + u);
+                gone |= ((b >> (l0 & 3)) & 1u) << u;
+            }
+        }
+        // lane h: alpha and gl from them; al is the coefficient of the feature gradient, alpha,
+        // under DROP alpha * d
         auto finish = [&](float (&al)[U], float (&gl)[U]) {
 #pragma unroll
             for (int u = 0; u < U; ++u) al[u] = gl[u] = 0.f;
@@ -127,7 +150,13 @@ __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *q
                 for (int u = 0; u < U; ++u) {
                     const float p = expf(lg[u] - hd.shift);
                     al[u] = hon ? p / hd.sum : 0.f;
-                    gl[u] = al[u] * (ga[u] - hd.t);  // a pad head: 0 * (0 - 0)
+                    if constexpr (DROP) {
+                        const float d = (gone >> u) & 1u ? 0.f : dm.scale;
+                        gl[u] = al[u] * (d * ga[u] - hd.t);
+                        al[u] *= d;
+                    } else {
+                        gl[u] = al[u] * (ga[u] - hd.t);  // a pad head: 0 * (0 - 0)
+                    }
                 }
             }
         };
@@ -263,14 +292,14 @@ __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *q
     }
 }
 
-template <int KG, int HP, int U>
+template <int KG, int HP, int U, bool DROP>
 __global__ __launch_bounds__(kBlock) void datb_walk_kernel(
     const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
     const float *__restrict__ q, float scale, const uint8_t *__restrict__ rec, int RS,
     const float *__restrict__ out, const float *__restrict__ row_max,
     const float *__restrict__ row_sum, const float *__restrict__ grad_out, float *__restrict__ T,
     float *__restrict__ glT, int num_rows, int64_t num_e, int D, int DS, int k, int chunk,
-    int n_items, int H, int flags) {
+    int n_items, int H, int flags, MaskArg<DROP> dm) {
     // flags: bit 0 16-B loads of grad_out and out, bit 1 of q (D % 4 == 0, 16-B aligned)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int wid = threadIdx.x / kWave;
@@ -309,8 +338,8 @@ __global__ __launch_bounds__(kBlock) void datb_walk_kernel(
             }
             stage_query(qrow, q, r, num_rows, H, D, DS, scale, qvec, lane);
             wave_lds_fence();
-            walk_piece_bwd<KG, HP, U>(grow, qrow, DS, col_idx, rec, RS, T, glT, H, D, (int)p.sb,
-                                      (int)p.se, k, hd, lane);
+            walk_piece_bwd<KG, HP, U, DROP>(grow, qrow, DS, col_idx, rec, RS, T, glT, H, D,
+                                            (int)p.sb, (int)p.se, k, hd, lane, dm);
         }
         ++r;
         if (r >= num_rows) break;
@@ -470,13 +499,14 @@ DotBwdLayout bwd_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D
     return L;
 }
 
-template <int HP>
+template <int HP, bool DROP>
 int launch_dot_bwd(const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr,
                    const int32_t *csc_eid, const float *q, float scale, const float *cbsr_val,
                    const uint8_t *cbsr_idx, const float *out, const float *row_max,
                    const float *row_sum, const float *grad_out, float *grad_q, float *grad_cbsr,
                    int64_t num_rows, int64_t num_cols, int64_t num_e, int D, int k, int H,
-                   int chunk_edges, const DotBwdLayout &L, void *workspace, hipStream_t s) {
+                   int chunk_edges, const DotBwdLayout &L, void *workspace, hipStream_t s,
+                   const MaskArg<DROP> &dm) {
     const RecordGeom &R = L.R;
     char *ws = reinterpret_cast<char *>(workspace);
     float *T = reinterpret_cast<float *>(ws);
@@ -491,10 +521,10 @@ int launch_dot_bwd(const int32_t *row_ptr, const int32_t *col_idx, const int32_t
         (D % 4 == 0 && ((uintptr_t)q & 15) == 0 ? 2 : 0);
     bool ok = with_const<8, 16, 32, 64>(R.kg, [&](auto kg_c) {
         constexpr int KG = decltype(kg_c)::value;
-        hipLaunchKernelGGL((datb_walk_kernel<KG, HP, MAXK_DATB_U>), item_grid(L.n_items),
+        hipLaunchKernelGGL((datb_walk_kernel<KG, HP, MAXK_DATB_U, DROP>), item_grid(L.n_items),
                            dim3(kBlock), L.lds_a, s, row_ptr, col_idx, q, scale, rec, R.RS, out,
                            row_max, row_sum, grad_out, T, glT, (int)num_rows, num_e, D, R.DS, k,
-                           L.chunk, L.n_items, H, aflags);
+                           L.chunk, L.n_items, H, aflags, dm);
     });
     if (!ok) return bad_lanes(R.kg);
     MAXK_LAUNCHED("datb_walk_kernel");
@@ -528,14 +558,15 @@ extern "C" size_t maxk_dot_attention_heads_backward_workspace_size(
     return bwd_layout(num_rows, num_cols, num_e, dim_origin, dim_k, num_heads, chunk_edges).total;
 }
 
-extern "C" int maxk_dot_attention_heads_backward(
+namespace {
+// Both backward entries; dm: the dropout entry's mask, null for none.
+int dot_attention_heads_backward(
     const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr, const int32_t *csc_eid,
     const float *q, float scale, const float *cbsr_val, const uint8_t *cbsr_idx, const float *out,
     const float *row_max, const float *row_sum, const float *grad_out, float *grad_q,
     float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
     int32_t dim_k, int32_t num_heads, int32_t chunk_edges, void *workspace,
-    size_t workspace_bytes, void *stream) {
-    clear_error();
+    size_t workspace_bytes, void *stream, const DropMask *dm) {
     if (int rc = check_dot(num_rows, num_cols, num_e, scale, dim_origin, dim_k, num_heads,
                            chunk_edges))
         return rc;
@@ -564,14 +595,62 @@ extern "C" int maxk_dot_attention_heads_backward(
                      ((uintptr_t)row_sum & 3) == 0 && ((uintptr_t)grad_out & 3) == 0 &&
                      ((uintptr_t)grad_q & 3) == 0 && ((uintptr_t)grad_cbsr & 3) == 0,
                  "float buffers must be 4-B aligned");
-#define MAXK_DATB(HP)                                                                           \
-    launch_dot_bwd<HP>(row_ptr, col_idx, col_ptr, csc_eid, q, scale, cbsr_val, cbsr_idx, out,   \
-                       row_max, row_sum, grad_out, grad_q, grad_cbsr, num_rows, num_cols, num_e, \
-                       D, k, H, chunk_edges, L, workspace, s)
+#define MAXK_DATB(HP, DROP, DM)                                                                 \
+    launch_dot_bwd<HP, DROP>(row_ptr, col_idx, col_ptr, csc_eid, q, scale, cbsr_val, cbsr_idx,  \
+                             out, row_max, row_sum, grad_out, grad_q, grad_cbsr, num_rows,      \
+                             num_cols, num_e, D, k, H, chunk_edges, L, workspace, s, DM)
+    if (dm) {
+        switch (L.hp) {
+            case 2: return MAXK_DATB(2, true, *dm);
+            case 4: return MAXK_DATB(4, true, *dm);
+            default: return MAXK_DATB(8, true, *dm);
+        }
+    }
     switch (L.hp) {
-        case 2: return MAXK_DATB(2);
-        case 4: return MAXK_DATB(4);
-        default: return MAXK_DATB(8);
+        case 2: return MAXK_DATB(2, false, NoMask{});
+        case 4: return MAXK_DATB(4, false, NoMask{});
+        default: return MAXK_DATB(8, false, NoMask{});
     }
 #undef MAXK_DATB
+}
+}  // namespace
+
+extern "C" int maxk_dot_attention_heads_backward(
+    const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr, const int32_t *csc_eid,
+    const float *q, float scale, const float *cbsr_val, const uint8_t *cbsr_idx, const float *out,
+    const float *row_max, const float *row_sum, const float *grad_out, float *grad_q,
+    float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+    int32_t dim_k, int32_t num_heads, int32_t chunk_edges, void *workspace,
+    size_t workspace_bytes, void *stream) {
+    clear_error();
+    return dot_attention_heads_backward(row_ptr, col_idx, col_ptr, csc_eid, q, scale, cbsr_val,
+                                        cbsr_idx, out, row_max, row_sum, grad_out, grad_q,
+                                        grad_cbsr, num_rows, num_cols, num_e, dim_origin, dim_k,
+                                        num_heads, chunk_edges, workspace, workspace_bytes, stream,
+                                        nullptr);
+}
+
+extern "C" size_t maxk_dot_attention_heads_dropout_backward_workspace_size(
+    int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+    int32_t num_heads, int32_t chunk_edges) {
+    return maxk_dot_attention_heads_backward_workspace_size(num_rows, num_cols, num_e, dim_origin,
+                                                            dim_k, num_heads, chunk_edges);
+}
+
+extern "C" int maxk_dot_attention_heads_dropout_backward(
+    const int32_t *row_ptr, const int32_t *col_idx, const int32_t *col_ptr, const int32_t *csc_eid,
+    const float *q, float scale, const float *cbsr_val, const uint8_t *cbsr_idx, const float *out,
+    const float *row_max, const float *row_sum, const float *grad_out, float *grad_q,
+    float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+    int32_t dim_k, int32_t num_heads, int32_t chunk_edges, float p, uint64_t seed,
+    void *workspace, size_t workspace_bytes, void *stream) {
+    clear_error();
+    if (int rc = check_dropout(p)) return rc;
+    // p == 0 drops nothing and scales by 1: the kernels of the entry without dropout
+    const DropMask dm = drop_mask(p, seed);
+    return dot_attention_heads_backward(row_ptr, col_idx, col_ptr, csc_eid, q, scale, cbsr_val,
+                                        cbsr_idx, out, row_max, row_sum, grad_out, grad_q,
+                                        grad_cbsr, num_rows, num_cols, num_e, dim_origin, dim_k,
+                                        num_heads, chunk_edges, workspace, workspace_bytes, stream,
+                                        p > 0.f ? &dm : nullptr);
 }

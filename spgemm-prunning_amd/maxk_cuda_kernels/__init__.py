@@ -775,7 +775,7 @@ def _dot_operands(indptr, indices, q, cbsr_val, cbsr_idx, D, scale, validate):
 def dot_attention_heads(indptr: torch.Tensor, indices: torch.Tensor, q: torch.Tensor,
                         cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor, dim_origin: int,
                         scale: float, chunk: int = 0, validate: Optional[bool] = None,
-                        out: Optional[torch.Tensor] = None):
+                        out: Optional[torch.Tensor] = None, dropout: float = 0.0, seed: int = 0):
     """(out [H, num_rows, D], row_max [H, num_rows], row_sum [H, num_rows]): scaled dot-product
     attention of H heads on CBSR keys in one walk of the graph (maxk_dot_attention_heads).  The
     logit of edge (r <- c) is scale * sum_l cbsr_val[c, l] * q[h, r, cbsr_idx[c, l]], q
@@ -784,7 +784,10 @@ def dot_attention_heads(indptr: torch.Tensor, indices: torch.Tensor, q: torch.Te
     the scale, H edge_softmax calls and spgemm_forward_heads compute, without logits or
     coefficients [H, E] ever being stored.  row_max and row_sum are the softmax statistics of
     every row and head; dot_edge_alpha_heads rebuilds the coefficients from them.
-    1 <= H <= MAX_HEADS; scale finite and > 0; bitwise repeatable."""
+    1 <= H <= MAX_HEADS; scale finite and > 0; bitwise repeatable.
+    dropout > 0: attention dropout at that rate under the mask of (seed, head, edge)
+    (maxk_dot_attention_heads_dropout; edge_dropout_heads has the contract): out sums
+    alpha * d * value, the statistics stay those of the undropped softmax."""
     D = int(dim_origin)
     H, num_rows, num_cols, k, scale = _dot_operands(indptr, indices, q, cbsr_val, cbsr_idx, D,
                                                     scale, validate)
@@ -793,9 +796,16 @@ def dot_attention_heads(indptr: torch.Tensor, indices: torch.Tensor, q: torch.Te
     row_max = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
     row_sum = torch.empty(H, num_rows, dtype=torch.float32, device=dev)
     shape = (num_rows, num_cols, indices.numel(), D, k, H, chunk)
-    _launch_ws(dev, "maxk_dot_attention_heads", "maxk_dot_attention_heads_workspace_size", shape,
-               (_ptr(indptr), _ptr(indices), _ptr(q), scale, _ptr(cbsr_val), _ptr(cbsr_idx),
-                _ptr(out), _ptr(row_max), _ptr(row_sum), *shape))
+    args = (_ptr(indptr), _ptr(indices), _ptr(q), scale, _ptr(cbsr_val), _ptr(cbsr_idx),
+            _ptr(out), _ptr(row_max), _ptr(row_sum), *shape)
+    if dropout > 0:
+        _launch_ws(dev, "maxk_dot_attention_heads_dropout",
+                   "maxk_dot_attention_heads_dropout_workspace_size", shape,
+                   args + _dropout_args(dropout, seed))
+    else:
+        _dropout_args(dropout, seed)
+        _launch_ws(dev, "maxk_dot_attention_heads", "maxk_dot_attention_heads_workspace_size",
+                   shape, args)
     return out, row_max, row_sum
 
 
@@ -828,7 +838,8 @@ def dot_attention_heads_backward(indptr: torch.Tensor, indices: torch.Tensor, q:
                                  cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor,
                                  out: torch.Tensor, row_max: torch.Tensor, row_sum: torch.Tensor,
                                  grad_output: torch.Tensor, scale: float, chunk: int = 0,
-                                 validate: Optional[bool] = None, plan=None):
+                                 validate: Optional[bool] = None, plan=None,
+                                 dropout: float = 0.0, seed: int = 0):
     """(grad_q [H, num_rows, D], grad_cbsr [num_cols, k]) of dot_attention_heads from its three
     results and the gradient of `out`, in one call (maxk_dot_attention_heads_backward): what
     dot_edge_alpha_heads, edge_weight_grad_heads, H edge_softmax_backward calls,
@@ -836,7 +847,8 @@ def dot_attention_heads_backward(indptr: torch.Tensor, indices: torch.Tensor, q:
     allocated.  The row sum of the softmax backward is taken as the dot product of out[h, r] and
     grad_output[h, r], so `out` must be the forward's.  Uses the graph's transpose plan (cached
     per `indices`, or `plan=` from transpose_plan()).  Bitwise repeatable; the same operand
-    checks as dot_attention_heads."""
+    checks as dot_attention_heads.  dropout, seed: those of the forward that produced `out`
+    (maxk_dot_attention_heads_dropout_backward); the row sum is still that dot product."""
     _need(grad_output, "grad_output", torch.float32)
     _need(out, "out", torch.float32)
     _need(q, "q", torch.float32)
@@ -856,11 +868,17 @@ def dot_attention_heads_backward(indptr: torch.Tensor, indices: torch.Tensor, q:
     grad_q = torch.empty(H, num_rows, D, dtype=torch.float32, device=dev)
     grad_cbsr = torch.empty(num_cols, k, dtype=torch.float32, device=dev)
     shape = (num_rows, num_cols, indices.numel(), D, k, H, chunk)
-    _launch_ws(dev, "maxk_dot_attention_heads_backward",
-               "maxk_dot_attention_heads_backward_workspace_size", shape,
-               (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(q), scale,
-                _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), _ptr(row_max), _ptr(row_sum),
-                _ptr(grad_output), _ptr(grad_q), _ptr(grad_cbsr), *shape))
+    args = (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(q), scale,
+            _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(out), _ptr(row_max), _ptr(row_sum),
+            _ptr(grad_output), _ptr(grad_q), _ptr(grad_cbsr), *shape)
+    if dropout > 0:
+        _launch_ws(dev, "maxk_dot_attention_heads_dropout_backward",
+                   "maxk_dot_attention_heads_dropout_backward_workspace_size", shape,
+                   args + _dropout_args(dropout, seed))
+    else:
+        _dropout_args(dropout, seed)
+        _launch_ws(dev, "maxk_dot_attention_heads_backward",
+                   "maxk_dot_attention_heads_backward_workspace_size", shape, args)
     return grad_q, grad_cbsr
 
 

@@ -117,21 +117,24 @@ class CSRGraph:
                                         seed)
 
     def dot_attend_heads(self, topk_values, topk_indices, dim: int, q, scale: float,
-                         backward: str = "rebuilt"):
+                         backward: str = "rebuilt", dropout: float = 0.0, seed: int = 0):
         """[H, V, dim]: scaled dot-product attention of H heads on the CBSR keys, from the
         queries q [H, V, dim] mapped into the feature space, with the score and the softmax
         inside the aggregation walk (maxk_dot_attention_heads): what maxk_dot_scores_heads, the
         edge softmax per head and aggregate_heads give, without logits or alpha [H, E] stored.
         backward: "rebuilt" (alpha as a transient of the backward) or "fused" (one
         dot_attention_heads_backward call, no [H, E] tensor in the backward either);
-        MAXK_DOT_ATTN_BWD=fused|rebuilt overrides it."""
+        MAXK_DOT_ATTN_BWD=fused|rebuilt overrides it.
+        dropout, seed: attention dropout inside the walk under the mask of (seed, head, edge)
+        (mk.edge_dropout_heads has the contract); only the two numbers are kept for the
+        backward, which recomputes the mask."""
         if backward not in ("rebuilt", "fused"):
             raise ValueError(f'backward must be "rebuilt" or "fused", got {backward!r}')
         forced = os.environ.get("MAXK_DOT_ATTN_BWD", "")
         if forced in ("fused", "rebuilt"):
             backward = forced
         return maxk_dot_attention_heads(self.indptr, self.indices, q, topk_values, topk_indices,
-                                        dim, scale, backward)
+                                        dim, scale, backward, dropout, seed)
 
 
 class MaxK(Function):
@@ -657,13 +660,21 @@ class MaxKTransformerConv(nn.Module):
 
     attn_drop: dropout of alpha after the softmax's normalisation, in training mode, under the
     mask of (seed, head, edge) (mk.edge_dropout_heads); forward(..., attn_seed=) fixes the seed.
-    The stored path only: the fused walk has no dropout yet and raises a ValueError."""
+    By default the stored path only: the fused walk then raises a ValueError in training mode.
+
+    fused_attn_drop=True opts into the dropout inside the fused walk: in training mode with
+    attn_drop > 0 and the fused attention the layer calls CSRGraph.dot_attend_heads(...,
+    dropout=attn_drop, seed=...) in either backward mode -- the same mask as the stored path's
+    for the same seed, only the two numbers kept for the backward and no [H, E] tensor anywhere
+    with the fused backward.  In eval() or with attn_drop == 0 the keyword changes nothing.
+    Flipping its default, which would retire the ValueError, is left to a later change."""
 
     def __init__(self, in_feats: int, out_feats: int, num_heads: int, bias: bool = True,
                  activation=None, attention: str = "stored", attn_drop: float = 0.0,
-                 attention_backward: str = "rebuilt"):
+                 attention_backward: str = "rebuilt", fused_attn_drop: bool = False):
         super().__init__()
         self.attn_drop = _check_attn_drop(attn_drop)
+        self.fused_attn_drop = bool(fused_attn_drop)
         if attention not in ("stored", "fused"):
             raise ValueError(f'attention must be "stored" or "fused", got {attention!r}')
         if attention_backward not in ("rebuilt", "fused"):
@@ -702,13 +713,18 @@ class MaxKTransformerConv(nn.Module):
         H, O, I = self.num_heads, self.out_feats, self.in_feats
         p = self.attn_drop if self.training else 0.0
         fused = self.attention_mode() == "fused"
-        if fused and p > 0:
+        if fused and p > 0 and not self.fused_attn_drop:
             raise ValueError("MaxKTransformerConv: the fused walk has no dropout yet; use "
-                             'attention="stored" with attn_drop > 0')
+                             'attention="stored" with attn_drop > 0, or opt into the masked '
+                             "fused walk with fused_attn_drop=True")
         Wq, Wk, Wv = (fc.weight.view(H, O, I) for fc in (self.fc_q, self.fc_k, self.fc_v))
         # (W_q x_v) . (W_k x_u) = ((x_v W_q^T) W_k) . x_u: the query in the feature space
         q = torch.matmul(torch.matmul(x_sparse, Wq.transpose(1, 2)), Wk)  # [H, V, in]
-        if fused:
+        if fused and p > 0:
+            agg = graph.dot_attend_heads(topk_values, topk_indices, I, q, self.scale,
+                                         self.attention_backward_mode(), dropout=p,
+                                         seed=attn_seed_of(attn_seed))
+        elif fused:
             agg = graph.dot_attend_heads(topk_values, topk_indices, I, q, self.scale,
                                          self.attention_backward_mode())
         else:

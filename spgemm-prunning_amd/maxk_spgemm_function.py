@@ -597,11 +597,17 @@ class MaxKDotAttentionHeadsFunction(Function):
     well and runs one maxk_cuda_kernels.dot_attention_heads_backward call instead: no tensor of
     H * E elements in the backward either.  It falls back to the rebuilt backward when not both
     gradients are needed, when the table is too large for the entry
-    (maxk_cuda_kernels.HEADS_MAX_COLS) and when MAXK_BWD_MODE forces a backward mode."""
+    (maxk_cuda_kernels.HEADS_MAX_COLS) and when MAXK_BWD_MODE forces a backward mode.
+
+    dropout, seed (a ninth and tenth argument, default 0.0 and 0): attention dropout under the
+    mask of (seed, head, edge) that maxk_cuda_kernels.edge_dropout_heads documents.  Only the two
+    numbers are kept: the forward walk evaluates the mask, the fused backward evaluates it again
+    in its one call, and the rebuilt backward masks the coefficients' gradient before the softmax
+    backward and the rebuilt coefficients after it, for the feature gradient."""
 
     @staticmethod
     def forward(ctx, graph_indptr, graph_indices, q, topk_values, topk_indices, dim_origin, scale,
-                backward="rebuilt"):
+                backward="rebuilt", dropout=0.0, seed=0):
         _require_kernels()
         if backward not in ("rebuilt", "fused"):
             raise ValueError(f'backward must be "rebuilt" or "fused", got {backward!r}')
@@ -609,8 +615,10 @@ class MaxKDotAttentionHeadsFunction(Function):
                                                      topk_indices)
         ctx.scale = float(scale)
         ctx.q_dtype = q.dtype
+        ctx.drop = (float(dropout), int(seed))
         out, row_max, row_sum = maxk_cuda_kernels.dot_attention_heads(
-            indptr, indices, qf, vals, sel, int(dim_origin), ctx.scale)
+            indptr, indices, qf, vals, sel, int(dim_origin), ctx.scale, dropout=ctx.drop[0],
+            seed=ctx.drop[1])
         V, k = vals.shape
         ctx.fused_bwd = (backward == "fused" and V < maxk_cuda_kernels.HEADS_MAX_COLS
                          and maxk_cuda_kernels.graph_only_mode(k, indices.numel(), V) is not None)
@@ -627,14 +635,18 @@ class MaxKDotAttentionHeadsFunction(Function):
         mk = maxk_cuda_kernels
         g = _f32_grad(grad_output)
         H, _, D = qf.shape
+        p, seed = ctx.drop
         if ctx.fused_bwd and all(ctx.needs_input_grad[2:4]):
             grad_q, grad_tv = mk.dot_attention_heads_backward(
                 indptr, indices, qf, vals, sel, ctx.saved_tensors[7], row_max, row_sum, g,
-                ctx.scale)
-            return None, None, grad_q.to(ctx.q_dtype), grad_tv, None, None, None, None
+                ctx.scale, dropout=p, seed=seed)
+            return (None, None, grad_q.to(ctx.q_dtype), grad_tv, None, None, None, None, None,
+                    None)
         alpha = mk.dot_edge_alpha_heads(indptr, indices, qf, vals, sel, D, ctx.scale, row_max,
                                         row_sum)
         grad_a = mk.edge_weight_grad_heads(indptr, indices, vals, sel, g)
+        if p > 0:  # the gradient of the dropped coefficients back through the mask
+            mk.edge_dropout_heads(grad_a, p, seed, out=grad_a)
         grad_l = torch.empty_like(grad_a)
         for h in range(H):
             mk.edge_softmax_backward(indptr, alpha[h], grad_a[h], out=grad_l[h])
@@ -644,23 +656,27 @@ class MaxKDotAttentionHeadsFunction(Function):
             grad_q = mk.spgemm_forward_heads(indptr, indices, grad_l, vals, sel, D)
             grad_q = grad_q.mul_(ctx.scale).to(ctx.q_dtype)
         if ctx.needs_input_grad[3]:
+            if p > 0:  # the softmax backward above took the undropped coefficients
+                mk.edge_dropout_heads(alpha, p, seed, out=alpha)
             grad_tv = mk.sspmm_backward_heads(indptr, indices, alpha, g, sel)
             grad_tv.add_(mk.sspmm_backward_heads(indptr, indices, grad_l, qf, sel),
                          alpha=ctx.scale)
         del alpha, grad_l
-        return None, None, grad_q, grad_tv, None, None, None, None
+        return None, None, grad_q, grad_tv, None, None, None, None, None, None
 
 
 def maxk_dot_attention_heads(graph_indptr, graph_indices, q, topk_values, topk_indices,
-                             dim_origin, scale, backward="rebuilt"):
+                             dim_origin, scale, backward="rebuilt", dropout=0.0, seed=0):
     """[H, V, dim_origin] = sum over a row's edges of softmax(scale * q[h, row] .
     scatter(topk)[col]) * scatter(topk)[col], for the H heads of one CSR graph, without logits or
     coefficients [H, E] being stored; gradients for q and topk_values
     (MaxKDotAttentionHeadsFunction).  backward: "rebuilt" (the coefficients as a transient and
-    the stored path's passes) or "fused" (one dot_attention_heads_backward call)."""
+    the stored path's passes) or "fused" (one dot_attention_heads_backward call).  dropout,
+    seed: attention dropout inside the walk, the mask recomputed by each backward."""
     _require_kernels()
     return MaxKDotAttentionHeadsFunction.apply(graph_indptr, graph_indices, q, topk_values,
-                                               topk_indices, dim_origin, scale, backward)[0]
+                                               topk_indices, dim_origin, scale, backward, dropout,
+                                               seed)[0]
 
 
 class MaxKSpmmWrapper:

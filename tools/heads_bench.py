@@ -66,6 +66,14 @@ within every iteration so all of them see the same clocks and cache state:
                         for attention stored, fused with the rebuilt backward and fused with the
                         fused backward, with the peak memory of one step of each
 
+  dot_attention_dropout_fwd / dot_attention_fwd   mk.dot_attention_heads with dropout = 0.6
+                        against without: the mask's cost in the walk (--pairs dot_attention_dropout)
+  dot_attention_dropout_bwd / dot_attention_bwd   mk.dot_attention_heads_backward likewise
+  step_stored / step_fused_rebuilt / step_fused_fused   MaxKTransformerConv forward plus backward
+                        with attn_drop = 0.6: the stored path, what a user writes without
+                        fused_attn_drop, against the masked fused walk with either backward; the
+                        peak memory of one step of each
+
 It reports the medians, the ratio heads / calls of each pair, and the run-to-run spread of the
 single-head baselines in this run, (max - min) / median over the iterations: the heads kernel
 counts as faster only where 1 - ratio exceeds that spread.  For the feature gradient it also
@@ -81,6 +89,9 @@ timed.  Writes one JSON file and prints it.
                               --heads 1,2,4,8 --out FILE
   python tools/heads_bench.py --pairs dot_attention_bwd --graphs reddit:16,reddit:32,products:16,products:32
                               --heads 1,2,4,8 --out profiles/r20/dot_attention_bwd/bench.json
+  python tools/heads_bench.py --pairs dot_attention_dropout --graphs reddit:16,reddit:32,products:16,products:32
+                              --heads 1,2,4,8 --iters 10 --warmup 2
+                              --out profiles/r22/dot_attn_dropout/bench.json
 """
 import argparse
 import json
@@ -896,6 +907,118 @@ def run_dot_attention_bwd(name, k, D, H, iters, warmup, seed, dev):
     return r
 
 
+def run_dot_attention_dropout(name, k, D, H, iters, warmup, seed, dev, p=0.6):
+    """The mask's cost: mk.dot_attention_heads and mk.dot_attention_heads_backward with
+    dropout = p against the same calls without, alternating inside every iteration; then
+    MaxKTransformerConv's training step with attn_drop = p: the stored path (what a user writes
+    without fused_attn_drop) against the masked fused walk with the rebuilt and with the fused
+    backward, and the peak memory of one step of each."""
+    import maxk_layers as ML
+    V = bench.maxk_graph.PRESETS[name]["V"]
+    row_ptr, col = _graph(name, seed, dev)
+    E = col.numel()
+    gen = torch.Generator(device=dev).manual_seed(655)
+    q = torch.randn(H, V, D, generator=gen, device=dev)
+    cv, ci = mk.topk_cbsr(torch.rand(V, D, generator=gen, device=dev), k)
+    G = torch.randn(H, V, D, generator=gen, device=dev)
+    scale = float(D // H) ** -0.5
+    y = torch.empty(H, V, D, device=dev)
+    plan = mk.transpose_plan(col, V)
+    mseed = 0x5EED0001
+    fw = {False: mk.dot_attention_heads(row_ptr, col, q, cv, ci, D, scale, validate=True),
+          True: mk.dot_attention_heads(row_ptr, col, q, cv, ci, D, scale, validate=False,
+                                       dropout=p, seed=mseed)}
+    keep = {}
+
+    def fwd(drop):
+        mk.dot_attention_heads(row_ptr, col, q, cv, ci, D, scale, out=y, validate=False,
+                               dropout=p if drop else 0.0, seed=mseed)
+
+    def bwd(drop):
+        keep[drop] = mk.dot_attention_heads_backward(
+            row_ptr, col, q, cv, ci, *fw[drop], G, scale, validate=False, plan=plan,
+            dropout=p if drop else 0.0, seed=mseed)
+
+    ops = (("dot_attention_dropout_fwd", lambda: fwd(True)),
+           ("dot_attention_fwd", lambda: fwd(False)),
+           ("dot_attention_dropout_bwd", lambda: bwd(True)),
+           ("dot_attention_bwd", lambda: bwd(False)))
+    for _ in range(warmup):
+        for _, fn in ops:
+            fn()
+    torch.cuda.synchronize()
+    ts = {n: [] for n, _ in ops}
+    for _ in range(iters):
+        for n, fn in ops:
+            ts[n].append(timed(fn))
+    s = {n: summary(t) for n, t in ts.items()}
+    r = dict(kind="dot_attention_dropout", graph=name, V=V, E=E, D=D, k=k, H=H, p=p, scale=scale,
+             **s)
+    r["dropped_fraction_of_out_zero"] = float((fw[True][0] == 0).float().mean()
+                                              - (fw[False][0] == 0).float().mean())
+    for what in ("fwd", "bwd"):
+        ratio = (s[f"dot_attention_dropout_{what}"]["median_ms"]
+                 / s[f"dot_attention_{what}"]["median_ms"])
+        spread = s[f"dot_attention_{what}"]["spread"]
+        r[f"ratio_dot_attention_dropout_{what}_to_plain"] = round(ratio, 4)
+        r[f"dot_attention_dropout_{what}_slower"] = bool(ratio - 1.0 > spread)
+    keep.clear()
+    del fw, G, y, q
+    torch.cuda.empty_cache()
+
+    graph = ML.CSRGraph(row_ptr, col)
+    torch.manual_seed(7)
+    conv = ML.MaxKTransformerConv(D, D // H, H, attn_drop=p, fused_attn_drop=True).to(dev)
+    xs, vals, idx = ML.maxk(torch.rand(V, D, device=dev), k)
+    xs = xs.detach().requires_grad_(True)
+    vals = vals.detach().requires_grad_(True)
+    modes = {"stored": ("stored", "rebuilt"), "fused_rebuilt": ("fused", "rebuilt"),
+             "fused_fused": ("fused", "fused")}
+
+    def step(mode):
+        conv.attention, conv.attention_backward = modes[mode]
+        conv.zero_grad(set_to_none=True)
+        xs.grad = vals.grad = None
+        conv(graph, xs, vals, idx, attn_seed=mseed).sum().backward()
+
+    saved = {v: os.environ.pop(v, None) for v in ("MAXK_DOT_ATTN", "MAXK_DOT_ATTN_BWD")}
+    try:
+        for _ in range(warmup):
+            for mode in modes:
+                step(mode)
+        torch.cuda.synchronize()
+        tl = {mode: [] for mode in modes}
+        for _ in range(iters):
+            for mode in modes:
+                tl[mode].append(timed(lambda: step(mode)))
+        for mode in modes:  # the peak of one step, the other modes' buffers released
+            conv.zero_grad(set_to_none=True)
+            xs.grad = vals.grad = None
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            step(mode)
+            torch.cuda.synchronize()
+            r[f"step_{mode}_peak_bytes"] = int(torch.cuda.max_memory_allocated())
+            r[f"step_{mode}_peak_over_resident_bytes"] = int(torch.cuda.max_memory_allocated()
+                                                             - base)
+    finally:
+        for v, x in saved.items():
+            if x is not None:
+                os.environ[v] = x
+    sl = {f"step_{mode}": summary(t) for mode, t in tl.items()}
+    r.update(sl)
+    r["alpha_bytes"] = 4 * H * E
+    for a in ("fused_rebuilt", "fused_fused"):
+        ratio = sl[f"step_{a}"]["median_ms"] / sl["step_stored"]["median_ms"]
+        spread = sl["step_stored"]["spread"]
+        r[f"ratio_step_{a}_to_stored"] = round(ratio, 4)
+        r[f"step_{a}_faster"] = bool(1.0 - ratio > spread)
+        r[f"step_{a}_slower"] = bool(ratio - 1.0 > spread)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--graphs", default="reddit:16,products:32")
@@ -936,6 +1059,9 @@ def main():
             if "dot_attention_bwd" in asked:
                 rs.append(run_dot_attention_bwd(name, int(k), args.dim, H, args.iters,
                                                 args.warmup, args.seed, dev))
+            if "dot_attention_dropout" in asked:
+                rs.append(run_dot_attention_dropout(name, int(k), args.dim, H, args.iters,
+                                                    args.warmup, args.seed, dev))
             if "layer" in asked and H >= 2:
                 rs.append(run_layer(name, int(k), args.dim, H, args.iters, args.warmup,
                                     args.seed, dev))
