@@ -901,6 +901,59 @@ int maxk_sspmm_backward_heads(const int32_t *row_ptr, const int32_t *col_idx,
                               int32_t num_heads, int32_t chunk_edges, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Max aggregation on CBSR features.  With X = scatter(CBSR) [num_cols, dim_origin] (zeros where
+ * a row keeps nothing):
+ *   out[r, j] = max over the edges e of row r of X[col_idx[e], j]     0 for a row without edges
+ *   arg[r, j] = the CSR edge index of the winner, or -1
+ * Candidates of (r, j): the row's edges whose column keeps j, in CSR order.  A repeated selector
+ * is folded into its first occurrence, which carries the sum of the values in l order (as for
+ * the sums); a selector >= dim_origin is no candidate.  The first candidate with the largest
+ * value wins (strict >: the lower edge index wins a tie, and -0.0 ties +0.0).  If at least one
+ * edge of the row does not keep j, its implicit +0.0 competes: it wins only when 0 > best
+ * strictly, or when there is no candidate at all -- an explicit value wins a tie against it --
+ * and then arg = -1 and out = +0.0; a row without edges has arg = -1 too.  out carries the
+ * winner's bits (the sign of a winning -0.0 is kept).  A NaN candidate wins over everything, the
+ * first NaN in edge order (torch's amax rule); out is then a quiet NaN, not the candidate's
+ * payload.  +Inf and -Inf order as values.
+ * arg may be NULL: no winners are stored (inference; saves 4 * num_rows * dim_origin bytes).
+ * Every element of out and, when given, of arg is written; num_e == 0 writes zeros and -1.
+ * Contract: the maximum is exact and the tie rule is stated in edge order, so out and arg are
+ * bitwise independent of chunk_edges, of where a hub row is cut over work items and of what
+ * the workspace held.
+ * Shapes: any 1 <= dim_k <= dim_origin <= 256, num_rows != num_cols allowed; a table past 2^24
+ * columns or 4 GiB of packed records is rejected.  chunk_edges as maxk_spgemm_forward.
+ * workspace: packed CBSR records + two key rows (8 * dim_origin bytes each) per work item.
+ *
+ * Backward:
+ *   grad_cbsr[c, l] = sum over the edges e = (r <- c), in CSC slot order, of
+ *                     [arg[r, cbsr_idx[c,l]] == e] * grad_out[r, cbsr_idx[c,l]]
+ * Every slot of the winning edge's column whose selector is j receives the gradient (a repeated
+ * selector's slots each do, as in the sums' backward).  A slot with a selector >= dim_origin, a
+ * column no edge reads and a slot that never won give an exact 0; a NaN of grad_out at an (r, j)
+ * whose arg names another edge or -1 reaches nothing.  Every element of grad_cbsr is written.
+ * Bitwise repeatable: no atomics in global memory, each sum runs in CSC slot order in fp32.
+ * col_ptr / csc_eid: maxk_transpose_plan's.  The row of every CSC slot is not a planned input:
+ * the call derives it from row_ptr into its workspace (4 * num_e bytes).  col_idx is unused and
+ * may be NULL.
+ * ------------------------------------------------------------------------- */
+size_t maxk_spgemm_max_forward_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                              int32_t dim_origin, int32_t dim_k,
+                                              int32_t chunk_edges);
+int maxk_spgemm_max_forward(const int32_t *row_ptr, const int32_t *col_idx, const float *cbsr_val,
+                            const uint8_t *cbsr_idx, float *out, int32_t *arg, int64_t num_rows,
+                            int64_t num_cols, int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                            int32_t chunk_edges, void *workspace, size_t workspace_bytes,
+                            void *stream);
+size_t maxk_spgemm_max_backward_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                               int32_t dim_origin, int32_t dim_k);
+int maxk_spgemm_max_backward(const int32_t *row_ptr, const int32_t *col_idx,
+                             const int32_t *col_ptr, const int32_t *csc_eid,
+                             const uint8_t *cbsr_idx, const int32_t *arg, const float *grad_out,
+                             float *grad_cbsr, int64_t num_rows, int64_t num_cols, int64_t num_e,
+                             int32_t dim_origin, int32_t dim_k, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
 /* Transpose plan of a CSR graph (once per graph): col_ptr[num_cols+1] of the
  * CSC and csc_eid[num_e] = the CSR edge id held by CSC slot t (stable in CSR order).
  * Replaces the CSC side files of generate_meta_csc.py:14-93 /

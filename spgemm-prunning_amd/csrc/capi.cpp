@@ -3,6 +3,7 @@
 #include <cstdio>
 
 #include "common.h"
+#include "spgemm_max.h"
 
 namespace maxk {
 namespace {
@@ -57,4 +58,43 @@ extern "C" int maxk_device_count(void) {
         return 0;
     }
     return n;
+}
+
+// ---- max aggregation (spgemm_max.hip) ----
+extern "C" size_t maxk_spgemm_max_forward_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                         int64_t num_e, int32_t dim_origin,
+                                                         int32_t dim_k, int32_t chunk_edges) {
+    return maxk::max_forward_workspace_size(num_rows, num_cols, num_e, dim_origin, dim_k,
+                                            chunk_edges);
+}
+
+extern "C" int maxk_spgemm_max_forward(const int32_t *row_ptr, const int32_t *col_idx,
+                                       const float *cbsr_val, const uint8_t *cbsr_idx, float *out,
+                                       int32_t *arg, int64_t num_rows, int64_t num_cols,
+                                       int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                                       int32_t chunk_edges, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+    maxk::clear_error();
+    return maxk::max_forward(row_ptr, col_idx, cbsr_val, cbsr_idx, out, arg, num_rows, num_cols,
+                             num_e, dim_origin, dim_k, chunk_edges, workspace, workspace_bytes,
+                             stream);
+}
+
+extern "C" size_t maxk_spgemm_max_backward_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                          int64_t num_e, int32_t dim_origin,
+                                                          int32_t dim_k) {
+    return maxk::max_backward_workspace_size(num_rows, num_cols, num_e, dim_origin, dim_k);
+}
+
+extern "C" int maxk_spgemm_max_backward(const int32_t *row_ptr, const int32_t *col_idx,
+                                        const int32_t *col_ptr, const int32_t *csc_eid,
+                                        const uint8_t *cbsr_idx, const int32_t *arg,
+                                        const float *grad_out, float *grad_cbsr, int64_t num_rows,
+                                        int64_t num_cols, int64_t num_e, int32_t dim_origin,
+                                        int32_t dim_k, void *workspace, size_t workspace_bytes,
+                                        void *stream) {
+    maxk::clear_error();
+    return maxk::max_backward(row_ptr, col_idx, col_ptr, csc_eid, cbsr_idx, arg, grad_out,
+                              grad_cbsr, num_rows, num_cols, num_e, dim_origin, dim_k, workspace,
+                              workspace_bytes, stream);
 }

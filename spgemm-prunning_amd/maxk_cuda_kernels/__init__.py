@@ -54,6 +54,7 @@ __all__ = [
     "gat_attention_heads_backward", "heads_attention_backward_route", "edge_dropout_heads",
     "dot_attention_heads", "dot_edge_alpha_heads", "dot_attention_heads_backward",
     "dot_attention_backward_route",
+    "spgemm_max_forward", "spgemm_max_backward",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -880,6 +881,55 @@ def dot_attention_heads_backward(indptr: torch.Tensor, indices: torch.Tensor, q:
         _launch_ws(dev, "maxk_dot_attention_heads_backward",
                    "maxk_dot_attention_heads_backward_workspace_size", shape, args)
     return grad_q, grad_cbsr
+
+
+def spgemm_max_forward(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
+                       idx: torch.Tensor, dim: int, chunk: int = 0, want_arg: bool = True,
+                       validate: Optional[bool] = None):
+    """(out [num_rows, dim] float32, arg [num_rows, dim] int32 or None): the element-wise maximum
+    over each row's neighbours of scatter(vals, idx) (maxk_spgemm_max_forward), and the CSR edge
+    index of every winner, -1 where the implicit zero of a neighbour that does not keep the
+    column wins or the row has no edges.  The first largest candidate in edge order wins, a NaN
+    beats everything (torch's amax); include/maxk_hip.h has the rules.  out and arg are bitwise
+    independent of `chunk`.  want_arg=False stores no winners (inference)."""
+    D = int(dim)
+    num_rows, num_cols, k = _heads_operands(indptr, indices, vals, idx, None, validate, D)
+    dev = vals.device
+    out = torch.empty(num_rows, D, dtype=torch.float32, device=dev)
+    arg = torch.empty(num_rows, D, dtype=torch.int32, device=dev) if want_arg else None
+    shape = (num_rows, num_cols, indices.numel(), D, k, int(chunk))
+    _launch_ws(dev, "maxk_spgemm_max_forward", "maxk_spgemm_max_forward_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(vals), _ptr(idx), _ptr(out), _ptr(arg), *shape))
+    return out, arg
+
+
+def spgemm_max_backward(indptr: torch.Tensor, indices: torch.Tensor, idx: torch.Tensor,
+                        arg: torch.Tensor, grad_out: torch.Tensor, k: int,
+                        plan=None) -> torch.Tensor:
+    """grad_vals [num_cols, k] of spgemm_max_forward from its `arg` and the gradient of `out`
+    (maxk_spgemm_max_backward): slot (c, l) receives grad_out[r, idx[c, l]] of every edge
+    (r <- c) that won its column, summed in CSC slot order; bitwise repeatable.  Uses the graph's
+    transpose plan (cached per `indices`, or `plan=` from transpose_plan())."""
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (idx, "sparse_selector", torch.uint8), (arg, "arg", torch.int32),
+                     (grad_out, "grad_out", torch.float32)):
+        _need(t, n, dt)
+    k = int(k)
+    if idx.dim() != 2 or idx.shape[1] != k:
+        raise RuntimeError("sparse_selector must be [num_cols, k]")
+    num_cols = idx.shape[0]
+    num_rows = indptr.numel() - 1
+    if grad_out.dim() != 2 or grad_out.shape[0] != num_rows or arg.shape != grad_out.shape:
+        raise RuntimeError("arg and grad_out must be [num_rows, dim_origin]")
+    D = grad_out.shape[1]
+    dev = grad_out.device
+    col_ptr, csc_eid = plan if plan is not None else transpose_plan(indices, num_cols)
+    grad_vals = torch.empty(num_cols, k, dtype=torch.float32, device=dev)
+    shape = (num_rows, num_cols, indices.numel(), D, k)
+    _launch_ws(dev, "maxk_spgemm_max_backward", "maxk_spgemm_max_backward_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(idx), _ptr(arg),
+                _ptr(grad_out), _ptr(grad_vals), *shape))
+    return grad_vals
 
 
 def dot_attention_backward_route(num_heads: int, num_rows: int, num_e: int, k: int) -> str:

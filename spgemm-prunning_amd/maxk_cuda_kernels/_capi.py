@@ -130,6 +130,12 @@ SIGNATURES = {
                                                                  _i32, _i32, _i32, _i32,
                                                                  ctypes.c_float, ctypes.c_uint64,
                                                                  _p, _sz, _p]),
+    "maxk_spgemm_max_forward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
+    "maxk_spgemm_max_forward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32,
+                                               _i32, _i32, _p, _sz, _p]),
+    "maxk_spgemm_max_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32]),
+    "maxk_spgemm_max_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
+                                                _i32, _i32, _p, _sz, _p]),
     "maxk_sspmm_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
     "maxk_sspmm_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                            _i32, _i32, _i32, _p, _sz, _p]),

@@ -42,7 +42,7 @@ from torch.autograd import Function
 import maxk_cuda_kernels as mk
 from maxk_spgemm_function import (maxk_dot_attention_heads, maxk_dot_scores_heads,
                                   maxk_edge_dropout_heads, maxk_gat_attention_heads, maxk_spgemm,
-                                  maxk_spgemm_heads)
+                                  maxk_spgemm_heads, maxk_spgemm_max)
 
 
 def _clamped(graph, name: str) -> torch.Tensor:
@@ -89,6 +89,12 @@ class CSRGraph:
         return maxk_spgemm(self.indices, self.values if values is None else values,
                            topk_values, topk_indices, None, 0, self.indptr, row_div,
                            dim_origin=dim)
+
+    def aggregate_max(self, topk_values, topk_indices, dim: int):
+        """[V, dim]: the element-wise maximum over each row's neighbours of scatter(CBSR)
+        (maxk_spgemm_max): a neighbour that does not keep a column competes with 0 there, a row
+        without edges is 0.  Unweighted: the graph's edge values are not used."""
+        return maxk_spgemm_max(self.indptr, self.indices, topk_values, topk_indices, dim)
 
     def aggregate_heads(self, topk_values, topk_indices, dim: int, values, row_div=None):
         """[H, V, dim]: aggregate() for the H weight sets values [H, E] (attention heads), one
@@ -261,13 +267,27 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
 
 
 class MaxKSAGEConv(nn.Module):
-    """GraphSAGE-mean on MaxK features (model_integrated_v3.py:62-192):
-    rst = fc_self(x_sparse) + fc_neigh(mean_{u in N(v)} x_sparse[u])."""
+    """GraphSAGE on MaxK features (model_integrated_v3.py:62-192).
+    aggregator_type="mean": rst = fc_self(x_sparse) + fc_neigh(mean_{u in N(v)} x_sparse[u]).
+    aggregator_type="pool" (DGL's SAGEConv pool aggregator, which the reference's layer surface
+    names and hands to DGL): rst = fc_self(x_sparse) + fc_neigh(max_{u in N(v)} p[u]) with
+    p = MaxK_pool_k(fc_pool(x_sparse)).  MaxK stands where DGL's ReLU stands: the pooled
+    features are made k-sparse by the layer's own nonlinearity, which is what lets the maximum
+    run on the CBSR (CSRGraph.aggregate_max; a neighbour that does not keep a column competes
+    with 0 there, as its masked dense feature would).  pool_k: the k of that MaxK (default: the
+    k of the topk_values passed in).  fc_pool is Xavier-initialised with the ReLU gain, as DGL
+    does.  "mean" keeps its parameters, their initialisation and its state_dict keys."""
 
     def __init__(self, in_feats: int, out_feats: int, bias: bool = True, feat_drop: float = 0.,
                  activation=None, norm: Optional[nn.Module] = None,
-                 reference_compat: bool = False):
+                 reference_compat: bool = False, aggregator_type: str = "mean",
+                 pool_k: Optional[int] = None):
         super().__init__()
+        valid_aggre_types = {"mean", "pool"}
+        if aggregator_type not in valid_aggre_types:
+            raise ValueError(f"Invalid aggregator_type. Must be one of {valid_aggre_types}. "
+                             f"But got {aggregator_type!r} instead.")
+        self.aggregator_type, self.pool_k = aggregator_type, pool_k
         self.in_feats, self.out_feats = in_feats, out_feats
         self.reference_compat = reference_compat
         self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
@@ -277,6 +297,9 @@ class MaxKSAGEConv(nn.Module):
         gain = nn.init.calculate_gain("relu")
         nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
         nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
+        if aggregator_type == "pool":  # after the others: "mean" draws the same numbers as ever
+            self.fc_pool = nn.Linear(in_feats, in_feats)
+            nn.init.xavier_uniform_(self.fc_pool.weight, gain=gain)
 
     def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices):
         deg = _clamped(graph, "in_degrees")
@@ -285,7 +308,11 @@ class MaxKSAGEConv(nn.Module):
         else:
             h_self, topk_values = _dropped_values(x_sparse, topk_values, topk_indices,
                                                   self.feat_drop)
-        agg = graph.aggregate(topk_values, topk_indices, self.in_feats, row_div=deg)
+        if self.aggregator_type == "pool":
+            _, pv, pi = maxk(self.fc_pool(h_self), self.pool_k or topk_values.shape[1])
+            agg = graph.aggregate_max(pv, pi, self.in_feats)
+        else:
+            agg = graph.aggregate(topk_values, topk_indices, self.in_feats, row_div=deg)
         # fc_self(x) + fc_neigh(agg) as one accumulated pair of GEMMs
         rst = linear(h_self, self.fc_self, agg, self.fc_neigh)
         if self.activation is not None:
@@ -353,12 +380,21 @@ class MaxKGraphConv(nn.Module):
 
 
 class MaxKGINConv(nn.Module):
-    """GIN-sum on MaxK features (model_integrated_v3.py:400-520):
-    rst = apply_func((1 + eps) x + sum_{u in N(v)} x_sparse[u])."""
+    """GIN on MaxK features (model_integrated_v3.py:400-520):
+    rst = apply_func((1 + eps) x + sum_{u in N(v)} x_sparse[u]); aggregator_type="max" (DGL's
+    GINConv max aggregator) takes the element-wise maximum of the neighbours' x_sparse instead
+    of their sum (CSRGraph.aggregate_max on the layer's own CBSR inputs).  "max" has no
+    reference behaviour to reproduce and is not combined with reference_compat."""
 
     def __init__(self, apply_func: Optional[nn.Module] = None, init_eps: float = 0.,
-                 learn_eps: bool = False, activation=None, reference_compat: bool = False):
+                 learn_eps: bool = False, activation=None, reference_compat: bool = False,
+                 aggregator_type: str = "sum"):
         super().__init__()
+        if aggregator_type not in ("sum", "max"):
+            raise KeyError(f"Aggregator type {aggregator_type} not recognized.")
+        if aggregator_type == "max" and reference_compat:
+            raise ValueError('aggregator_type="max" is not combined with reference_compat')
+        self.aggregator_type = aggregator_type
         self.apply_func, self.activation = apply_func, activation
         self.reference_compat = reference_compat
         if learn_eps:
@@ -369,7 +405,10 @@ class MaxKGINConv(nn.Module):
     def forward(self, graph: CSRGraph, x, topk_values, topk_indices):
         # reference_compat: the "sum" kernel call passes the in-degrees (:491-495), a mean
         row_div = _clamped(graph, "in_degrees") if self.reference_compat else None
-        neigh = graph.aggregate(topk_values, topk_indices, x.shape[1], row_div=row_div)
+        if self.aggregator_type == "max":
+            neigh = graph.aggregate_max(topk_values, topk_indices, x.shape[1])
+        else:
+            neigh = graph.aggregate(topk_values, topk_indices, x.shape[1], row_div=row_div)
         rst = (1 + self.eps) * x + neigh
         if self.apply_func is not None:
             rst = self.apply_func(rst)

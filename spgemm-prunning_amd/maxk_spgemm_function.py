@@ -679,6 +679,53 @@ def maxk_dot_attention_heads(graph_indptr, graph_indices, q, topk_values, topk_i
                                                seed)[0]
 
 
+class MaxKSpGEMMMaxFunction(Function):
+    """The element-wise maximum over each row's neighbours of scatter(topk_values, topk_indices):
+    apply(graph_indptr, graph_indices, topk_values [V, k], topk_indices [V, k], dim_origin)
+    -> out [V, dim_origin] (maxk_cuda_kernels.spgemm_max_forward has the rules: the first
+    largest candidate in edge order wins, a neighbour that does not keep a column competes with
+    an implicit zero, a NaN beats everything).
+
+    The forward saves the winners' edge indices arg [V, dim_origin] int32 and topk_indices, and
+    nothing else of the activations (the graph's own tensors ride on the context); when
+    topk_values needs no gradient -- it does not require one, or (a sixth argument, which
+    maxk_spgemm_max passes: grad mode is always off inside a forward) grad mode is off -- the
+    kernel stores no winners at all.  The backward is one maxk_cuda_kernels.spgemm_max_backward call: the gradient reaches
+    topk_values only, each winner's slots receiving grad_output at their column."""
+
+    @staticmethod
+    def forward(ctx, graph_indptr, graph_indices, topk_values, topk_indices, dim_origin,
+                grad_mode=True):
+        _require_kernels()
+        indptr, indices = _i32(graph_indptr), _i32(graph_indices)
+        sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
+        sel = sel.contiguous()
+        want = bool(grad_mode and ctx.needs_input_grad[2])
+        out, arg = maxk_cuda_kernels.spgemm_max_forward(indptr, indices, _f32_act(topk_values),
+                                                        sel, int(dim_origin), want_arg=want)
+        if want:
+            ctx.graph = (indptr, indices)
+            ctx.val_dtype = topk_values.dtype
+            ctx.save_for_backward(arg, sel)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        arg, sel = ctx.saved_tensors
+        indptr, indices = ctx.graph
+        grad = maxk_cuda_kernels.spgemm_max_backward(indptr, indices, sel, arg,
+                                                     _f32_grad(grad_output), sel.shape[1])
+        return None, None, grad.to(ctx.val_dtype), None, None, None
+
+
+def maxk_spgemm_max(graph_indptr, graph_indices, topk_values, topk_indices, dim_origin):
+    """[V, dim_origin] = max over a row's neighbours of scatter(topk)[col], 0 for a row without
+    edges; the gradient reaches topk_values (MaxKSpGEMMMaxFunction)."""
+    _require_kernels()
+    return MaxKSpGEMMMaxFunction.apply(graph_indptr, graph_indices, topk_values, topk_indices,
+                                       dim_origin, torch.is_grad_enabled())
+
+
 class MaxKSpmmWrapper:
     """Holds the warp4 metadata of one graph (maxk_spgemm_function.py:214-267)."""
 
