@@ -88,4 +88,102 @@ __device__ __forceinline__ uint32_t drop_bits(const DropMask &dm, uint32_t e, ui
            (r[3] < dm.thr ? 8u : 0u);
 }
 
+// ---- the forward walks' mask: once in S wave steps ---------------------------------------------
+// A pass of the hub-row heads walk (heads_walk.h) holds EU = EP * U edges per wave step, and its
+// heads lie in qp <= 2 quads.  One Philox evaluation per lane -- lane t on the edge at offset
+// t % span of the next S = 64 / (EU * qp) steps (span = S * EU; its CSR position is the piece's
+// first edge + its index in the piece) and the quad q0 + t / span -- serves S steps: four
+// ballots, one per head of a quad, carry the bits, and each group keeps its head's 64 (`mine`).
+// The caller's sum of p takes the unmasked weights and its products p * keep (0 or 1): a dropped
+// NaN or Inf stays NaN.
+struct DropPass {
+    int q0, qp, head;  // the pass's first quad of heads and their number; the group's head
+};
+// The pass over the heads h0 .. min(h0 + HC, H), seen from the group of `head`.
+__device__ __forceinline__ DropPass drop_pass(int h0, int HC, int H, int head) {
+    return DropPass{h0 >> 2, ((min(h0 + HC, H) - 1) >> 2) - (h0 >> 2) + 1, head};
+}
+template <bool DROP>
+struct PassMask {  // without a mask: nothing
+    __device__ __forceinline__ PassMask(const DropPass &, int) {}
+    __device__ __forceinline__ void refresh(const NoMask &, const DropPass &, int, int) {}
+    __device__ __forceinline__ void next() {}
+};
+template <>
+struct PassMask<true> {
+    int EU, S, span_log, js = 0, qsel;
+    uint64_t mine = 0;
+    __device__ __forceinline__ PassMask(const DropPass &dp, int EU_) : EU(EU_) {
+        S = kWave / (EU * dp.qp);  // powers of two, EU * qp <= 64
+        span_log = 31 - __clz(S * EU);
+        qsel = min(max((dp.head >> 2) - dp.q0, 0), dp.qp - 1);
+    }
+    // Before the wave step whose first edge has the CSR position e0: every S-th step evaluates
+    // the masks of itself and the next S - 1 (js, S: wave-uniform).
+    __device__ __forceinline__ void refresh(const DropMask &dm, const DropPass &dp, int e0,
+                                            int lane) {
+        if (js == 0) {
+            const uint32_t bits = drop_bits(dm, (uint32_t)(e0 + (lane & ((1 << span_log) - 1))),
+                                            (uint32_t)(dp.q0 + (lane >> span_log)));
+            const uint64_t b0 = __ballot(bits & 1u), b1 = __ballot(bits & 2u),
+                           b2 = __ballot(bits & 4u), b3 = __ballot(bits & 8u);
+            const int hb = dp.head & 3;
+            mine = (hb == 0 ? b0 : hb == 1 ? b1 : hb == 2 ? b2 : b3) >> (qsel << span_log);
+        }
+    }
+    // 0 where the group's head of the step's edge slot (u * EP + eg) is dropped, else 1.
+    __device__ __forceinline__ float keep(int slot) const {
+        return (mine >> (js * EU + slot)) & 1 ? 0.f : 1.f;
+    }
+    __device__ __forceinline__ void next() { js = js + 1 == S ? 0 : js + 1; }
+};
+
+// ---- the backward walks' mask: every wave step -------------------------------------------------
+// A backward walk (piece_walk.h) has KG lanes per edge, lane h < HP of a group holding head h of
+// the group's U edges of a step.  Lane j < U * QP of a group evaluates the mask of the group's
+// edge j % U for the quad of heads j / U, QP = ceil(HP / 4) quads; lane h fetches its head's bit
+// with one shuffle per edge.  Returns, in lane h, bit u: head h of the group's edge u -- CSR
+// position e0 + u * G + grp, e0 the step's first edge -- is dropped.  0 without a mask.  grp, l0,
+// lane0: the lane's group, its place in it and the group's first lane.
+template <int KG, int HP, int U, bool DROP>
+__device__ __forceinline__ uint32_t step_gone(const MaskArg<DROP> &dm, int e0, int grp, int l0,
+                                              int lane0) {
+    uint32_t gone = 0u;
+    if constexpr (DROP) {
+        constexpr int G = kWave / KG, QP = (HP + 3) / 4;
+        static_assert(U * QP <= KG, "a group evaluates its step's masks in one round");
+        const uint32_t bits =
+            drop_bits(dm, (uint32_t)(e0 + (l0 % U) * G + grp), (uint32_t)((l0 / U) % QP));
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t b = __shfl(bits, lane0 + ((l0 >> 2) % QP) * U + u);
+            gone |= ((b >> (l0 & 3)) & 1u) << u;
+        }
+    }
+    return gone;
+}
+
+// ---- host: the entries' dispatch ----------------------------------------------------------------
+// f(const_t<HP>{}, mask) for the padded head count hp (2, 4 or 8), mask = *dm, or NoMask{} where
+// dm is null; returns what f returns.  In f, is_drop_v<decltype(mask)> is the DROP of MaskArg.
+template <class M>
+constexpr bool is_drop_v = std::is_same_v<std::decay_t<M>, DropMask>;
+template <class F>
+int with_heads_mask(int hp, const DropMask *dm, F &&f) {
+    int rc = MAXK_ERR_INVALID;
+    const bool ok = with_const<2, 4, 8>(hp, [&](auto hp_c) {
+        rc = dm ? f(hp_c, *dm) : f(hp_c, NoMask{});
+    });
+    if (!ok) set_error("unsupported padded head count %d", hp);
+    return rc;
+}
+// f(dm) for a dropout entry's (p, seed): dm null at p == 0, which drops nothing and scales by 1
+// -- the kernels of the entry without dropout.
+template <class F>
+int with_dropout(float p, uint64_t seed, F &&f) {
+    if (int rc = check_dropout(p)) return rc;
+    const DropMask dm = drop_mask(p, seed);
+    return f(p > 0.f ? &dm : nullptr);
+}
+
 }  // namespace maxk

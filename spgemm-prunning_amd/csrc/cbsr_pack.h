@@ -1,6 +1,7 @@
 // Packed CBSR records and the token-stream item size, shared by the kernels that gather one
 // record per edge: the forward (spgemm_fwd.hip), the edge-weight gradient (edge_grad.hip) and
-// the multi-head forwards and the GAT backward (through heads_walk.h).
+// the multi-head forwards and the attention backwards (through heads_walk.h and piece_walk.h).
+// RecordSlot is how every one of them addresses a slot of a record.
 // Each translation unit gets its own copy of the pack kernels (anonymous namespace, like
 // slab_fixup_kernel in common.h).
 #pragma once
@@ -196,6 +197,19 @@ struct PackedSrc {
     __device__ __forceinline__ int col(int s, int D, int trash) const {
         (void)D;
         return min(s, trash);
+    }
+};
+
+// Slot l of a k-slot record as a lane reads it.  ok: the record has the slot.  A lane past it
+// (l >= k) reads the last slot instead (lc, the clamped slot: no load leaves the record) and
+// contributes nothing.  The record's layout is spelled here and in the pack kernels alone.
+struct RecordSlot {
+    bool ok;
+    uint32_t lc;
+    __device__ __forceinline__ RecordSlot(int l, int k)
+        : ok(l < k), lc((uint32_t)(ok ? l : k - 1)) {}
+    __device__ __forceinline__ PackedSrc src(__amdgpu_buffer_rsrc_t rrs, int k, int RS) const {
+        return PackedSrc{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
     }
 };
 

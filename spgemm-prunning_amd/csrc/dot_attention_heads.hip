@@ -11,9 +11,9 @@
 // walk is the hub-row heads walk of heads_walk.h, shared with spgemm_fwd_heads.hip and
 // gat_attention_heads.hip (records packed once, token-stream items, one wavefront per item under
 // CutHubRows, KG lanes per group, G = 64 / KG LDS copies of the output row, the heads in passes
-// of HC, the fix-up of the cut rows; its rules are stated there); the logit is edge_grad.hip's
-// (the H rows q[h, r, :] of the piece staged side by side in LDS, one fma per slot and a fixed
-// butterfly per logit):
+// of HC, the fix-up of the cut rows; its rules are stated there); the logit is a record's dot
+// product with a staged row (piece_walk.h, dot_logit.h: the H rows q[h, r, :] of the piece staged
+// side by side in LDS, one fma per slot and a fixed butterfly per logit):
 //
 //  1. launch_cbsr_pack fills the workspace's records.
 //  2. dath_fwd_kernel, per row piece: the H query rows are staged as scale * q (one rounding per
@@ -37,8 +37,8 @@
 // the weight NaN and stored undivided.  A row without edges stores zeros in out and both
 // statistics.  A query column no neighbour selects is never read from LDS: a NaN there reaches
 // nothing (the pad columns [D, DS) hold zeros and a skipped selector carries the value 0).
-// maxk_dot_edge_alpha_heads is edge_grad.hip's heads walk (CutAtEnd, no slab) with the epilogue
-// w = exp(l - row_max) / row_sum in place of the row_div scale; its logit is sweep 1's.
+// maxk_dot_edge_alpha_heads is a staged-row walk (piece_walk.h: CutAtEnd, no slab) with the
+// epilogue w = exp(l - row_max) / row_sum; its logit is sweep 1's.
 // No global atomics, no LDS atomics; every sum has an order fixed by (graph, chunk, k, H), so the
 // result is bitwise repeatable, and head h's slice is computed from head h's query only.
 // LDS per wave: (H + G) * DS floats (16.6 KB at H = 8, G = 8, D = 256; 12.5 KB at k = 16).
@@ -49,8 +49,6 @@
 
 #include "attn_dropout.h"
 #include "dot_logit.h"
-#include "edge_softmax.h"
-#include "heads_walk.h"
 
 // Waves per SIMD the masked forward is compiled for (1: whatever its registers allow).
 #ifndef MAXK_DATH_DROP_WAVES
@@ -76,9 +74,8 @@ __device__ __forceinline__ void piece_max(const float *qrow, const int32_t *__re
         for (int u = 0; u < U; ++u)  // past the piece's end the column reads 0 (column 0's record)
             c[u] = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, (base + u * G + grp) * 4, 0, 0);
         if (k <= KG) {  // one slot per lane: the record is loaded once for all heads
-            const bool lok = l0 < k;
-            const uint32_t lc = (uint32_t)(lok ? l0 : k - 1);
-            const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+            const RecordSlot sl(l0, k);
+            const PackedSrc src = sl.src(rrs, k, RS);
             float v[U];
             int s[U];
 #pragma unroll
@@ -88,8 +85,8 @@ __device__ __forceinline__ void piece_max(const float *qrow, const int32_t *__re
                 if (h < H) {
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
-                        const float l =
-                            logit_sum<KG>(logit_term(v[u], s[u], qrow + h * DS, trash, lok, 0.f));
+                        const float l = lane_tree<KG, Sum>(
+                            dot_term(v[u], s[u], qrow + h * DS, trash, sl.ok, 0.f));
                         m[h] = fmaxf(m[h], base + u * G + grp < n ? l : -INFINITY);
                     }
                 }
@@ -99,7 +96,7 @@ __device__ __forceinline__ void piece_max(const float *qrow, const int32_t *__re
             for (int h = 0; h < kMaxH; ++h) {
                 if (h < H) {
                     float l[U];
-                    edge_logits<KG, U>(rrs, RS, c, qrow + h * DS, k, trash, l0, l);
+                    record_dots<KG, U>(rrs, RS, c, qrow + h * DS, k, trash, l0, l);
 #pragma unroll
                     for (int u = 0; u < U; ++u)
                         m[h] = fmaxf(m[h], base + u * G + grp < n ? l[u] : -INFINITY);
@@ -117,16 +114,8 @@ __device__ __forceinline__ void piece_max(const float *qrow, const int32_t *__re
 // head's logit against qh; returns the lane's sum of p (the same in every lane of a group).
 // active: the group has an edge slot and a head in this pass; else it writes its trash column
 // only.  POISON: p = NaN and nothing is summed (the rows whose z is no positive number).
-// DROP (attn_dropout.h), the scheme of gat_attention_heads.hip's walk_attn: a wave step holds
-// EP * U edges and the pass's heads lie in dp.qp <= 2 quads, so one Philox evaluation per lane --
-// lane t on the edge at offset t % span of the next S = 64 / (EP * U * qp) steps (span =
-// S * EP * U; its CSR position is sb + its index in the piece) and the quad dp.q0 + t / span --
-// serves S steps: four ballots, one per head of a quad, carry the bits, and each group keeps its
-// head's 64 (`mine`).  The sum of p takes the unmasked weights and the products p * (0 or 1): a
-// dropped NaN or Inf stays NaN.
-struct DropPass {
-    int q0, qp, head;  // the pass's first quad of heads and their number; the group's head
-};
+// DROP: the pass mask of attn_dropout.h (PassMask) multiplied into the products; the sum of p
+// takes the unmasked weights.
 template <int KG, int U, bool POISON, bool DROP>
 __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
                                           const int32_t *__restrict__ col_idx, float shift,
@@ -139,14 +128,7 @@ __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
     const auto crs = wave_buffer(col_idx + sb, (uint32_t)n * 4u);
     const auto rrs = wave_buffer(rec, 0xffffffffu);
     float ps = 0.f;
-    const int EU = EP * U;
-    int S = 1, span_log = 0, js = 0, qsel = 0;
-    uint64_t mine = 0;
-    if constexpr (DROP) {
-        S = kWave / (EU * dp.qp);  // powers of two, EU * qp <= 64
-        span_log = 31 - __clz(S * EU);
-        qsel = min(max((dp.head >> 2) - dp.q0, 0), dp.qp - 1);
-    }
+    PassMask<DROP> pm(dp, EP * U);
     for (int base = 0; base < n; base += EP * U) {
         int c[U];
 #pragma unroll
@@ -154,24 +136,14 @@ __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
             c[u] = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, (base + u * EP + eg) * 4, 0, 0);
         float keep[DROP ? U : 1];  // DROP: 0 where the group's head of slot u is dropped, else 1
         if constexpr (DROP) {
-            if (js == 0) {  // wave-uniform: the masks of this and the next S - 1 steps
-                const uint32_t bits =
-                    drop_bits(dm, (uint32_t)(sb + base + (lane & ((1 << span_log) - 1))),
-                              (uint32_t)(dp.q0 + (lane >> span_log)));
-                const uint64_t b0 = __ballot(bits & 1u), b1 = __ballot(bits & 2u),
-                               b2 = __ballot(bits & 4u), b3 = __ballot(bits & 8u);
-                const int hb = dp.head & 3;
-                mine = (hb == 0 ? b0 : hb == 1 ? b1 : hb == 2 ? b2 : b3) >> (qsel << span_log);
-            }
+            pm.refresh(dm, dp, sb + base, lane);
 #pragma unroll
-            for (int u = 0; u < U; ++u)
-                keep[u] = (mine >> (js * EU + u * EP + eg)) & 1 ? 0.f : 1.f;
-            js = js + 1 == S ? 0 : js + 1;
+            for (int u = 0; u < U; ++u) keep[u] = pm.keep(u * EP + eg);
+            pm.next();
         }
         if (k <= KG) {  // the slot's value and selector serve the logit and the product
-            const bool lok = l0 < k;
-            const uint32_t lc = (uint32_t)(lok ? l0 : k - 1);
-            const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+            const RecordSlot sl(l0, k);
+            const PackedSrc src = sl.src(rrs, k, RS);
             float v[U];
             int s[U];
 #pragma unroll
@@ -183,12 +155,12 @@ __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
                 if constexpr (POISON) {
                     p = live ? NAN : 0.f;
                 } else {
-                    const float l = logit_sum<KG>(logit_term(v[u], s[u], qh, trash, lok, 0.f));
+                    const float l = lane_tree<KG, Sum>(dot_term(v[u], s[u], qh, trash, sl.ok, 0.f));
                     p = live ? expf(l - shift) : 0.f;
                     ps += p;
                     if constexpr (DROP) p *= keep[u];
                 }
-                float *a = &acc_g[live && lok ? min(s[u], trash) : trash];
+                float *a = &acc_g[live && sl.ok ? min(s[u], trash) : trash];
                 *a = __builtin_fmaf(p, v[u], *a);
             }
         } else {
@@ -198,7 +170,7 @@ __device__ __forceinline__ float walk_dot(float *acc_g, const float *qh,
                 for (int u = 0; u < U; ++u) p[u] = active && base + u * EP + eg < n ? NAN : 0.f;
             } else {
                 float l[U];
-                edge_logits<KG, U>(rrs, RS, c, qh, k, trash, l0, l);
+                record_dots<KG, U>(rrs, RS, c, qh, k, trash, l0, l);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     p[u] = active && base + u * EP + eg < n ? expf(l[u] - shift) : 0.f;
@@ -268,8 +240,7 @@ __global__ __launch_bounds__(kBlock, DROP ? MAXK_DATH_DROP_WAVES : 1) void dath_
             if (n > 0)
                 ps = walk_dot<KG, U, false, DROP>(
                     g.acc_g, qh, col_idx, shift_of(mh), rec, RS, (int)sb, (int)se, k, DS - 1, g.EP,
-                    g.eg, active, lane, dm,
-                    DropPass{h0 >> 2, ((min(h0 + HC, H) - 1) >> 2) - (h0 >> 2) + 1, head});
+                    g.eg, active, lane, dm, drop_pass(h0, HC, H, head));
             const int bad = bad_heads<KG>(ps, g.EP, HC, h0, H);
             if (whole && n > 0 && bad) {  // rare: NaN wherever such a head's row has an addend
                 wave_lds_fence();
@@ -298,7 +269,7 @@ __global__ __launch_bounds__(kBlock, DROP ? MAXK_DATH_DROP_WAVES : 1) void dath_
 }
 
 // ---- w[h, e] = exp(l_he - row_max[h, r]) / row_sum[h, r] ----------------------------------------
-// edge_grad.hip's walk_piece_heads with the softmax epilogue: one record gather per edge for all
+// The staged-row walk of piece_walk.h with the softmax epilogue: one record gather per edge for all
 // heads, the logit by sweep 1's functions, a batch's results per head through the wave's 64
 // staging floats as one coalesced store in CSR order.  st: the piece's row statistics,
 // st[h] = shift_of(row_max[h, r]) and st[kMaxH + h] = row_sum[h, r].
@@ -321,10 +292,7 @@ __device__ __forceinline__ void walk_alpha(const float *qrow, float *stage, cons
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (l0 == 0) stage[u * G + grp] = expf(l[u] - shift) / z;
-        wave_lds_fence();
-        const int e = base + lane;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(stage[lane % (G * U)]), ors,
-                                              lane < G * U ? e * 4 : (int)0x80000000, 0, 0);
+        store_staged<KG, U>(stage, ors, base, lane);
     };
     for (int base = 0; base < n; base += G * U) {
         int c[U];
@@ -332,9 +300,8 @@ __device__ __forceinline__ void walk_alpha(const float *qrow, float *stage, cons
         for (int u = 0; u < U; ++u)
             c[u] = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, (base + u * G + grp) * 4, 0, 0);
         if (k <= KG) {
-            const bool lok = l0 < k;
-            const uint32_t lc = (uint32_t)(lok ? l0 : k - 1);
-            const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+            const RecordSlot sl(l0, k);
+            const PackedSrc src = sl.src(rrs, k, RS);
             float v[U];
             int s[U];
 #pragma unroll
@@ -343,13 +310,14 @@ __device__ __forceinline__ void walk_alpha(const float *qrow, float *stage, cons
                 float l[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u)
-                    l[u] = logit_sum<KG>(logit_term(v[u], s[u], qrow + h * DS, trash, lok, 0.f));
+                    l[u] = lane_tree<KG, Sum>(
+                        dot_term(v[u], s[u], qrow + h * DS, trash, sl.ok, 0.f));
                 leave(h, base, l);
             }
         } else {
             for (int h = 0; h < H; ++h) {
                 float l[U];
-                edge_logits<KG, U>(rrs, RS, c, qrow + h * DS, k, trash, l0, l);
+                record_dots<KG, U>(rrs, RS, c, qrow + h * DS, k, trash, l0, l);
                 leave(h, base, l);
             }
         }
@@ -557,13 +525,11 @@ extern "C" int maxk_dot_attention_heads_dropout(
     int32_t num_heads, int32_t chunk_edges, float p, uint64_t seed, void *workspace,
     size_t workspace_bytes, void *stream) {
     clear_error();
-    if (int rc = check_dropout(p)) return rc;
-    // p == 0 drops nothing and scales by 1: the kernels of the entry without dropout
-    const DropMask dm = drop_mask(p, seed);
-    return dot_attention_heads(row_ptr, col_idx, q, scale, cbsr_val, cbsr_idx, out, row_max,
-                               row_sum, num_rows, num_cols, num_e, dim_origin, dim_k, num_heads,
-                               chunk_edges, workspace, workspace_bytes, stream,
-                               p > 0.f ? &dm : nullptr);
+    return with_dropout(p, seed, [&](const DropMask *dm) {
+        return dot_attention_heads(row_ptr, col_idx, q, scale, cbsr_val, cbsr_idx, out, row_max,
+                                   row_sum, num_rows, num_cols, num_e, dim_origin, dim_k,
+                                   num_heads, chunk_edges, workspace, workspace_bytes, stream, dm);
+    });
 }
 
 extern "C" size_t maxk_dot_edge_alpha_heads_workspace_size(int64_t num_rows, int64_t num_cols,

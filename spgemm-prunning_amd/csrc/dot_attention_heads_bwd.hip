@@ -12,13 +12,13 @@
 //   grad_cbsr[c, l]  = sum_h sum_{e -> c} (alpha_he * grad_out[h, r, s] + scale * gl_he * q[h, r, s])
 //
 // t is the softmax backward's sum_e alpha_he * ga_he, which equals the dot product of the two
-// dense rows out[h, r, :] and grad_out[h, r, :] (gat_attention_heads_bwd.hip): every item
+// dense rows out[h, r, :] and grad_out[h, r, :] (stage_dot, piece_walk.h): every item
 // computes it for itself before it touches an edge, so a row cut over items needs no second walk.
 //
 //  1. launch_cbsr_pack fills the workspace's records.
-//  2. datb_walk_kernel (walk A), one wavefront per item of `chunk` tokens cut at the item's end
-//     (CutAtEnd, the partition and lane groups of gath_bwd_kernel): KG = pow2ceil(k) lanes per
-//     edge (8 .. 64), G = 64 / KG edges per wave step, U steps in flight.
+//  2. datb_walk_kernel (walk A), a staged-row walk (piece_walk.h): one wavefront per item of
+//     `chunk` tokens cut at the item's end (CutAtEnd), KG = pow2ceil(k) lanes per edge (8 .. 64),
+//     G = 64 / KG edges per wave step, U steps in flight.
 //     * per row piece: the H rows grad_out[h, r, :] and the H rows scale * q[h, r, :] staged side
 //       by side in the wave's LDS (2 * H * DS floats, the pad columns [D, DS) zero), out[h, r, :]
 //       streamed beside them, t_h reduced by the fixed 64-lane butterfly: the same number in
@@ -52,11 +52,9 @@
 
 #include "attn_dropout.h"
 #include "dot_logit.h"
-#include "edge_softmax.h"
-#include "heads_walk.h"
 #include "sspmm_bwd.h"
 
-// Wave steps of record loads in flight in walk A (the depth of gath_bwd_kernel).
+// Wave steps of record loads in flight in walk A.
 #ifndef MAXK_DATB_U
 #define MAXK_DATB_U 4
 #endif
@@ -64,43 +62,15 @@
 namespace maxk {
 namespace {
 
-// grow[0:D] = g[0:D]; returns this lane's part of sum_{j : o[j] != 0} o[j] * g[j].  One wave.
-// (gat_attention_heads_bwd.hip's stage_dot.)
-__device__ __forceinline__ float stage_dot(float *grow, const float *__restrict__ g,
-                                           const float *__restrict__ o, int D, bool vec,
-                                           int lane) {
-    float t = 0.f;
-    if (vec) {
-        for (int j = lane * 4; j < D; j += kWave * 4) {
-            const float4 gv = *reinterpret_cast<const float4 *>(&g[j]);
-            const float4 ov = *reinterpret_cast<const float4 *>(&o[j]);
-            *reinterpret_cast<float4 *>(&grow[j]) = gv;
-            t = ov.x != 0.f ? __builtin_fmaf(ov.x, gv.x, t) : t;
-            t = ov.y != 0.f ? __builtin_fmaf(ov.y, gv.y, t) : t;
-            t = ov.z != 0.f ? __builtin_fmaf(ov.z, gv.z, t) : t;
-            t = ov.w != 0.f ? __builtin_fmaf(ov.w, gv.w, t) : t;
-        }
-    } else {
-        for (int j = lane; j < D; j += kWave) {
-            const float gv = g[j], ov = o[j];
-            grow[j] = gv;
-            t = ov != 0.f ? __builtin_fmaf(ov, gv, t) : t;
-        }
-    }
-    return t;
-}
-
 // What lane h of a group holds of head h for the row being walked (pad heads: 0, 1, 0).
 struct HeadLane {
     float shift, sum, t;
 };
 
 // The edges [sb, se) (sb < se) of one row whose grad_out rows are staged in grow and whose scaled
-// query rows are staged in qrow: stores their T rows and glT vectors.  DROP (attn_dropout.h), as
-// gat_attention_heads_bwd.hip's walk: lane j < U * QP of a group evaluates the mask of the
-// group's edge j % U for the quad of heads j / U, QP = ceil(HP / 4) quads; lane h fetches its
-// head's bit with one shuffle per edge and keeps alpha * d beside alpha: T gains alpha * d * g
-// and gl = alpha * (d * ga - t), t from the dropped out.
+// query rows are staged in qrow: stores their T rows and glT vectors.  DROP: lane h takes its
+// head's bits of the step from step_gone (attn_dropout.h) and keeps alpha * d beside alpha:
+// T gains alpha * d * g and gl = alpha * (d * ga - t), t from the dropped out.
 template <int KG, int HP, int U, bool DROP>
 __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *qrow, int DS,
                                                const int32_t *__restrict__ col_idx,
@@ -128,18 +98,8 @@ __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *q
         float lg[U], ga[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) lg[u] = ga[u] = 0.f;
-        uint32_t gone = 0u;  // DROP, lane h: bit u, head h of the group's edge u is dropped
-        if constexpr (DROP) {
-            constexpr int QP = (HP + 3) / 4;
-            static_assert(U * QP <= KG, "a group evaluates its step's masks in one round");
-            const uint32_t bits = drop_bits(
-                dm, (uint32_t)(sb + base + (l0 % U) * G + grp), (uint32_t)((l0 / U) % QP));
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t b = __shfl(bits, lane0 + ((l0 >> 2) % QP) * U + u);
-                gone |= ((b >> (l0 & 3)) & 1u) << u;
-            }
-        }
+        // DROP, lane h: bit u, head h of the group's edge u is dropped
+        const uint32_t gone = step_gone<KG, HP, U, DROP>(dm, sb + base, grp, l0, lane0);
         // lane h: alpha and gl from them; al is the coefficient of the feature gradient, alpha,
         // under DROP alpha * d
         auto finish = [&](float (&al)[U], float (&gl)[U]) {
@@ -162,20 +122,15 @@ __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *q
         };
         float al[U], gl[U];
         if (k <= KG) {  // one slot per lane: the record is loaded once for all heads
-            const bool lok = l0 < k;
-            const uint32_t lc = (uint32_t)(lok ? l0 : k - 1);
-            const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+            const RecordSlot sl(l0, k);
+            const PackedSrc src = sl.src(rrs, k, RS);
             float v[U];
             int s[U], sr[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
-            uint32_t keep = 0u;  // bit u: the slot carries a (folded) value under a selector < D
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                keep |= (lok && s[u] < 0x100 ? 1u : 0u) << u;
-                const int raw = s[u] & 255;  // the caller's selector
-                sr[u] = raw < D ? raw : trash;
-            }
+            for (int u = 0; u < U; ++u) sr[u] = s[u];  // s stays for the logit
+            const uint32_t keep = caller_columns(sr, sl.ok, D, trash);
 #pragma unroll
             for (int h = 0; h < HP; ++h) {
                 if (h < H) {
@@ -183,7 +138,7 @@ __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *q
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const float l =
-                            logit_sum<KG>(logit_term(v[u], s[u], qh, trash, lok, 0.f));
+                            lane_tree<KG, Sum>(dot_term(v[u], s[u], qh, trash, sl.ok, 0.f));
                         // a slot without a kept value adds nothing, whatever x is
                         const float x = gh[sr[u]];
                         const float d = lane_tree<KG, Sum>((keep >> u) & 1u ? v[u] * x : 0.f);
@@ -206,33 +161,26 @@ __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *q
                     }
                 }
             }
-#pragma unroll
-            for (int u = 0; u < U; ++u)  // idle lanes and edges past the piece's end: dropped
-                __builtin_amdgcn_raw_buffer_store_b32(
-                    __float_as_uint(tc[u]), trs,
-                    lok ? ((base + u * G + grp) * k + l0) * 4 : (int)0x80000000, 0, MAXK_T_AUX);
+            store_t_rows<KG, U>(trs, tc, sl.ok, base, grp, k, l0);
         } else {  // k > 64 (KG == 64, one edge per wave step): passes over l
 #pragma unroll
             for (int h = 0; h < HP; ++h) {
                 if (h < H) {
                     const float *gh = grow + h * DS;
                     float l[U], acc[U];
-                    edge_logits<KG, U>(rrs, RS, c, qrow + h * DS, k, trash, l0, l);
+                    record_dots<KG, U>(rrs, RS, c, qrow + h * DS, k, trash, l0, l);
 #pragma unroll
                     for (int u = 0; u < U; ++u) acc[u] = 0.f;
                     for (int lb = 0; lb < k; lb += KG) {
-                        const int sl = lb + l0;
-                        const bool lok = sl < k;
-                        const uint32_t lc = (uint32_t)(lok ? sl : k - 1);
-                        const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc,
-                                            (uint32_t)RS};
+                        const RecordSlot sl(lb + l0, k);
+                        const PackedSrc src = sl.src(rrs, k, RS);
                         float v[U];
                         int s[U];
 #pragma unroll
                         for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
 #pragma unroll
                         for (int u = 0; u < U; ++u) {
-                            const bool keep = lok && s[u] < 0x100;
+                            const bool keep = sl.ok && s[u] < 0x100;
                             const float x = gh[min(s[u], trash)];
                             acc[u] = keep ? __builtin_fmaf(v[u], x, acc[u]) : acc[u];
                         }
@@ -247,19 +195,13 @@ __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *q
             }
             finish(al, gl);
             for (int lb = 0; lb < k; lb += KG) {
-                const int sl = lb + l0;
-                const bool lok = sl < k;
-                const uint32_t lc = (uint32_t)(lok ? sl : k - 1);
-                const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+                const RecordSlot sl(lb + l0, k);
+                const PackedSrc src = sl.src(rrs, k, RS);
                 float v[U], tc[U];
                 int s[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int raw = s[u] & 255;
-                    s[u] = raw < D ? raw : trash;
-                }
+                caller_columns(s, sl.ok, D, trash);
 #pragma unroll
                 for (int h = 0; h < HP; ++h) {
                     if (h < H) {
@@ -273,12 +215,7 @@ __device__ __forceinline__ void walk_piece_bwd(const float *grow, const float *q
                         }
                     }
                 }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    __builtin_amdgcn_raw_buffer_store_b32(
-                        __float_as_uint(tc[u]), trs,
-                        lok ? ((base + u * G + grp) * k + sl) * 4 : (int)0x80000000, 0,
-                        MAXK_T_AUX);
+                store_t_rows<KG, U>(trs, tc, sl.ok, base, grp, k, lb + l0);
             }
         }
         // one gl vector per edge from the group's HP lanes
@@ -460,8 +397,6 @@ __global__ __launch_bounds__(kBlock) void datb_gq_kernel(
 
 // ---- host ---------------------------------------------------------------------------------------
 
-// A piece's T rows are addressed through a descriptor of 4 * k * n bytes with 32-bit offsets.
-constexpr int kBwdMaxChunk = 1 << 20;
 // Resident waves per CU the items are sized for: walk A four per SIMD by VGPRs, B seven (the
 // multi-head forward's), fewer where the staged rows or the copies fill the LDS first.
 constexpr int kWalkResident = 16;
@@ -483,9 +418,7 @@ DotBwdLayout bwd_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D
     L.R = record_geom(num_cols, D, k);
     L.hp = hp_of(H);
     L.lds_a = (size_t)kWavesPerBlock * 2 * H * L.R.DS * sizeof(float);
-    const int by_lds = (int)(kPullLdsBytes / L.lds_a) * kWavesPerBlock;
-    L.chunk = fwd_chunk(num_rows, num_e, chunk, by_lds < kWalkResident ? by_lds : kWalkResident);
-    if (L.chunk > kBwdMaxChunk) L.chunk = kBwdMaxChunk;
+    L.chunk = walk_chunk(num_rows, num_e, chunk, L.lds_a, kWalkResident, kBwdMaxChunk);
     L.n_items = token_items(num_rows, num_e, L.chunk);
     L.hc = heads_per_pass(H, L.R.kg);
     L.lds_b = (size_t)kWavesPerBlock * (kWave / L.R.kg) * L.R.DS * sizeof(float);
@@ -595,23 +528,12 @@ int dot_attention_heads_backward(
                      ((uintptr_t)row_sum & 3) == 0 && ((uintptr_t)grad_out & 3) == 0 &&
                      ((uintptr_t)grad_q & 3) == 0 && ((uintptr_t)grad_cbsr & 3) == 0,
                  "float buffers must be 4-B aligned");
-#define MAXK_DATB(HP, DROP, DM)                                                                 \
-    launch_dot_bwd<HP, DROP>(row_ptr, col_idx, col_ptr, csc_eid, q, scale, cbsr_val, cbsr_idx,  \
-                             out, row_max, row_sum, grad_out, grad_q, grad_cbsr, num_rows,      \
-                             num_cols, num_e, D, k, H, chunk_edges, L, workspace, s, DM)
-    if (dm) {
-        switch (L.hp) {
-            case 2: return MAXK_DATB(2, true, *dm);
-            case 4: return MAXK_DATB(4, true, *dm);
-            default: return MAXK_DATB(8, true, *dm);
-        }
-    }
-    switch (L.hp) {
-        case 2: return MAXK_DATB(2, false, NoMask{});
-        case 4: return MAXK_DATB(4, false, NoMask{});
-        default: return MAXK_DATB(8, false, NoMask{});
-    }
-#undef MAXK_DATB
+    return with_heads_mask(L.hp, dm, [&](auto hp_c, const auto &mask) {
+        return launch_dot_bwd<decltype(hp_c)::value, is_drop_v<decltype(mask)>>(
+            row_ptr, col_idx, col_ptr, csc_eid, q, scale, cbsr_val, cbsr_idx, out, row_max, row_sum,
+            grad_out, grad_q, grad_cbsr, num_rows, num_cols, num_e, D, k, H, chunk_edges, L,
+            workspace, s, mask);
+    });
 }
 }  // namespace
 
@@ -645,12 +567,11 @@ extern "C" int maxk_dot_attention_heads_dropout_backward(
     int32_t dim_k, int32_t num_heads, int32_t chunk_edges, float p, uint64_t seed,
     void *workspace, size_t workspace_bytes, void *stream) {
     clear_error();
-    if (int rc = check_dropout(p)) return rc;
-    // p == 0 drops nothing and scales by 1: the kernels of the entry without dropout
-    const DropMask dm = drop_mask(p, seed);
-    return dot_attention_heads_backward(row_ptr, col_idx, col_ptr, csc_eid, q, scale, cbsr_val,
-                                        cbsr_idx, out, row_max, row_sum, grad_out, grad_q,
-                                        grad_cbsr, num_rows, num_cols, num_e, dim_origin, dim_k,
-                                        num_heads, chunk_edges, workspace, workspace_bytes, stream,
-                                        p > 0.f ? &dm : nullptr);
+    return with_dropout(p, seed, [&](const DropMask *dm) {
+        return dot_attention_heads_backward(row_ptr, col_idx, col_ptr, csc_eid, q, scale, cbsr_val,
+                                            cbsr_idx, out, row_max, row_sum, grad_out, grad_q,
+                                            grad_cbsr, num_rows, num_cols, num_e, dim_origin,
+                                            dim_k, num_heads, chunk_edges, workspace,
+                                            workspace_bytes, stream, dm);
+    });
 }

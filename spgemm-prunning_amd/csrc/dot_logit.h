@@ -1,58 +1,22 @@
 // The logit of the dot-product attention on CBSR keys, stated once for the walks that form it: both
 // sweeps of the fused forward and the alpha entry (dot_attention_heads.hip) and the fused backward
-// (dot_attention_heads_bwd.hip).  Every one of them calls these device functions on the same
-// staged row scale * q, so a logit has the same bits wherever it is formed: the forward's row
-// maximum is the exact maximum of what the alpha entry and the backward exponentiate, and
-// exp(l - row_max) <= 1 holds in all of them.  With them the argument checks the entries share.
+// (dot_attention_heads_bwd.hip).  It is the record's dot product of piece_walk.h -- dot_term and
+// lane_tree<KG, Sum> with one slot per lane, record_dots for k > 64 -- against the row scale * q
+// that stage_query stages.  Every one of them calls those device functions on that same staged
+// row, so a logit has the same bits wherever it is formed: the forward's row maximum is the exact
+// maximum of what the alpha entry and the backward exponentiate, and exp(l - row_max) <= 1 holds
+// in all of them.  With it the argument checks the entries share.
 // Device code in an anonymous namespace (each translation unit instantiates what it launches).
 #pragma once
 
 #include <cmath>
 
-#include "edge_softmax.h"
-#include "heads_walk.h"
+#include "piece_walk.h"
 
 namespace maxk {
 namespace {
 
 constexpr int kMaxH = MAXK_MAX_HEADS;
-
-// ---- the logit, shared by both sweeps of the forward and by the alpha walk ----------------------
-// One slot of an edge's dot product against the staged (scaled) query row qh: an idle lane's
-// clamped slot contributes nothing.
-__device__ __forceinline__ float logit_term(float v, int s, const float *qh, int trash, bool lok,
-                                            float acc) {
-    const float t = __builtin_fmaf(v, qh[min(s, trash)], acc);
-    return lok ? t : acc;
-}
-// The group's slots summed by the fixed butterfly of edge_grad.hip's group_sum: every lane of the
-// group holds the same bits.
-template <int KG>
-__device__ __forceinline__ float logit_sum(float acc) {
-    return lane_tree<KG, Sum>(acc);
-}
-// k > KG (k > 64): a lane takes its slots l0, l0 + KG, ... in l order, the record from the caches.
-template <int KG, int U>
-__device__ __forceinline__ void edge_logits(const __amdgpu_buffer_rsrc_t rrs, int RS,
-                                            const int (&c)[U], const float *qh, int k, int trash,
-                                            int l0, float (&l)[U]) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) l[u] = 0.f;
-    for (int lb = 0; lb < k; lb += KG) {
-        const int sl = lb + l0;
-        const bool lok = sl < k;
-        const uint32_t lc = (uint32_t)(lok ? sl : k - 1);
-        const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
-        float v[U];
-        int s[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
-#pragma unroll
-        for (int u = 0; u < U; ++u) l[u] = logit_term(v[u], s[u], qh, trash, lok, l[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) l[u] = logit_sum<KG>(l[u]);
-}
 
 // qrow[h * DS + j] = scale * q[h, row, j] for the H heads (the pad columns [D, DS) hold zeros and
 // are never staged over).  One wave.

@@ -32,7 +32,9 @@
 //       5.06 against 5.00 ms products-sized at k = 32, the latter inside the run-to-run
 //       spread: MAXK_EGRAD_LDS_STORE=0, profiles/r07/edge_grad/.)
 // No atomics, no allocation, copy or synchronisation: the launch can be captured.
-#include "heads_walk.h"  // the host side's record geometry and item size
+// The item driver is token_items.h's walk_cut_item; the staging, the group sum (lane_tree) and the
+// staged store are piece_walk.h's, shared with the attention backwards and the dot-product alpha.
+#include "piece_walk.h"
 
 #ifndef MAXK_EGRAD_U  // edge-gradient: wave steps of record loads in flight
 #define MAXK_EGRAD_U 8
@@ -43,41 +45,6 @@
 
 namespace maxk {
 namespace {
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) {
-    return __int_as_float(
-        __builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-
-// Sum over each aligned group of KG lanes, left in every lane of the group.  A butterfly of
-// fixed shape: both lanes of a pair add the same two numbers, so the group agrees bitwise.
-template <int KG>
-__device__ __forceinline__ float group_sum(float x) {
-    x += dpp_f<0xB1>(x);   // quad_perm [1,0,3,2]: lane ^ 1
-    x += dpp_f<0x4E>(x);   // quad_perm [2,3,0,1]: lane ^ 2
-    x += dpp_f<0x141>(x);  // row_half_mirror: the other quad of the 8 (all its lanes equal)
-    if constexpr (KG >= 16) x += dpp_f<0x140>(x);  // row_mirror: the other 8 of the 16
-    if constexpr (KG >= 32)  // ds_swizzle, bit mode, xor 0x10: the other 16 of the 32
-        x += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), 0x401F));
-    if constexpr (KG >= 64) {  // halves exchanged: r[0] = the low half's x, r[1] = the high's
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x),
-                                                        false, false);
-        x = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-    return x;
-}
-
-// grow[0:D] = G[row, :] (grow's pad columns [D, DS) already hold zeros).  One wave.
-__device__ __forceinline__ void stage_row(float *grow, const float *__restrict__ g, int D, bool vec,
-                                          int lane) {
-    if (vec) {
-        for (int j = lane * 4; j < D; j += kWave * 4)
-            *reinterpret_cast<float4 *>(&grow[j]) = *reinterpret_cast<const float4 *>(&g[j]);
-    } else {
-        for (int j = lane; j < D; j += kWave) grow[j] = g[j];
-    }
-}
 
 // grad_edge[e] = dot(record of col_idx[e], grow) / div over e in [sb, se), sb < se: a piece of
 // one row whose G row is staged in grow.  WIDE (tables past 2^24 columns or 4 GiB): 64-bit
@@ -103,32 +70,30 @@ __device__ __forceinline__ void walk_piece(const float *grow, float *stage,
             acc[u] = 0.f;
         }
         for (int lb = 0; lb < k; lb += KG) {  // one pass unless k > 64
-            const int l = lb + l0;
-            const bool lok = l < k;
-            const uint32_t lc = (uint32_t)(lok ? l : k - 1);
+            const RecordSlot sl(lb + l0, k);
             float v[U];
             int s[U];
             if constexpr (!WIDE) {
-                const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+                const PackedSrc src = sl.src(rrs, k, RS);
 #pragma unroll
                 for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
             } else {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const uint8_t *p = rec + (size_t)(uint32_t)c[u] * RS;
-                    v[u] = reinterpret_cast<const float *>(p)[lc];
-                    s[u] = reinterpret_cast<const uint16_t *>(p + 4 * k)[lc];
+                    v[u] = reinterpret_cast<const float *>(p)[sl.lc];
+                    s[u] = reinterpret_cast<const uint16_t *>(p + 4 * k)[sl.lc];
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const float t = __builtin_fmaf(v[u], grow[min(s[u], trash)], acc[u]);
-                acc[u] = lok ? t : acc[u];  // an idle lane's clamped slot contributes nothing
+                acc[u] = sl.ok ? t : acc[u];  // an idle lane's clamped slot contributes nothing
             }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const float x = group_sum<KG>(acc[u]);
+            const float x = lane_tree<KG, Sum>(acc[u]);
             acc[u] = scale ? x / div : x;
         }
         if constexpr (MAXK_EGRAD_LDS_STORE) {
@@ -137,10 +102,7 @@ __device__ __forceinline__ void walk_piece(const float *grow, float *stage,
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (l0 == 0) stage[u * G + grp] = acc[u];
-            wave_lds_fence();
-            const int e = base + lane;
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(stage[lane % (G * U)]), ors,
-                                                  lane < G * U ? e * 4 : (int)0x80000000, 0, 0);
+            store_staged<KG, U>(stage, ors, base, lane);
         } else {
             // lane 0 of each group: G consecutive floats per instruction; past the piece's end
             // (and from the other lanes) the offset is out of the descriptor's range: dropped
@@ -173,35 +135,23 @@ __global__ __launch_bounds__(kBlock) void edge_grad_kernel(
 
     const ItemRange it = item_range(row_ptr, num_rows, num_e, item, chunk);
 
-    // The item walks the edges whose tokens lie in [d0, d1) (CutAtEnd): first the tail of row
-    // r - 1 (its row token precedes d0), then the rows whose token it holds, the last one cut
-    // at d1.
-    int q = it.r - 1;
-    RowPiece p{0, 0, false};
-    if (it.r > 0) p = cont_piece(CutAtEnd{}, it.p_lo, it.d1, it.r, row_ptr[it.r]);
-    for (;;) {
-        const int64_t sb = p.sb, se = p.se;
-        if (q >= 0 && sb < se) {
-            const float div = row_div ? row_div[q] : 1.f;  // loaded before the walk
-            wave_lds_fence();  // the previous piece's reads of grow are done
-            stage_row(grow, grad_out + (int64_t)q * D, D, vec != 0, lane);
-            wave_lds_fence();
-            walk_piece<KG, U, WIDE>(grow, stage, col_idx, rec, RS, grad_edge, (int)sb, (int)se, k,
-                                    DS - 1, div, row_div != nullptr, lane);
-        }
-        ++q;
-        if (q >= num_rows) break;
-        const int64_t rb = row_ptr[q];
-        if (!row_owned(it.d1, q, rb)) break;  // row q's token belongs to a later item
-        p = row_piece(CutAtEnd{}, it.d1, q, rb, row_ptr[q + 1]);
-    }
+    // the edges whose tokens lie in [d0, d1), row piece by row piece
+    walk_cut_item(row_ptr, num_rows, it, [&](int q, int64_t sb, int64_t se, int64_t, bool) {
+        if (sb >= se) return;
+        const float div = row_div ? row_div[q] : 1.f;  // loaded before the walk
+        wave_lds_fence();  // the previous piece's reads of grow are done
+        stage_row(grow, grad_out + (int64_t)q * D, D, vec != 0, lane);
+        wave_lds_fence();
+        walk_piece<KG, U, WIDE>(grow, stage, col_idx, rec, RS, grad_edge, (int)sb, (int)se, k,
+                                DS - 1, div, row_div != nullptr, lane);
+    });
 }
 
 // ---- H heads (maxk_edge_weight_grad_heads): grad_out [H, num_rows, D], grad_edge [H, num_e] ----
 // The walk above with one record load per edge serving every head: per row piece the H rows
 // G[h, r, :] are staged side by side (grow[h * DS + j]: H * DS floats per wave, 8.3 KB at H = 8,
 // D = 256); per edge the lane's value and selector are loaded once and each head takes one fma
-// against its staged row and the same fixed-shape group_sum, so head h's result is, bitwise,
+// against its staged row and the same fixed-shape lane_tree, so head h's result is, bitwise,
 // what the single-head kernel gives for G[h] (H = 1: the same kernel in effect).  For k > 64
 // (several slots per lane) the passes over l run per head and the record is loaded again from
 // the caches.  A batch's results leave per head through the wave's 64 staging floats as one
@@ -218,22 +168,16 @@ __device__ __forceinline__ void walk_piece_heads(const float *grow, float *stage
     const int n = se - sb;  // wave-uniform, <= chunk
     const auto crs = wave_buffer(col_idx + sb, (uint32_t)n * 4u);
     const auto rrs = wave_buffer(rec, 0xffffffffu);
-    // head h's finished sums of the batch at `base`: scaled, staged in edge order, one store
-    auto leave = [&](int h, int base, float (&acc)[U]) {
+    // head h's sums of the batch at `base`: scaled, staged in edge order, one store
+    auto leave = [&](int h, int base, float (&x)[U]) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float x = group_sum<KG>(acc[u]);
-            acc[u] = scale ? x / div : x;
-        }
+        for (int u = 0; u < U; ++u) x[u] = scale ? x[u] / div : x[u];
         const auto ors = wave_buffer(grad_edge + (int64_t)h * num_e + sb, (uint32_t)n * 4u);
         wave_lds_fence();
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (l0 == 0) stage[u * G + grp] = acc[u];
-        wave_lds_fence();
-        const int e = base + lane;
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(stage[lane % (G * U)]), ors,
-                                              lane < G * U ? e * 4 : (int)0x80000000, 0, 0);
+            if (l0 == 0) stage[u * G + grp] = x[u];
+        store_staged<KG, U>(stage, ors, base, lane);
     };
     for (int base = 0; base < n; base += G * U) {
         int c[U];
@@ -241,9 +185,8 @@ __device__ __forceinline__ void walk_piece_heads(const float *grow, float *stage
         for (int u = 0; u < U; ++u)
             c[u] = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, (base + u * G + grp) * 4, 0, 0);
         if (k <= KG) {  // one slot per lane: the record is loaded once for all heads
-            const bool lok = l0 < k;
-            const uint32_t lc = (uint32_t)(lok ? l0 : k - 1);
-            const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+            const RecordSlot sl(l0, k);
+            const PackedSrc src = sl.src(rrs, k, RS);
             float v[U];
             int s[U];
 #pragma unroll
@@ -257,31 +200,15 @@ __device__ __forceinline__ void walk_piece_heads(const float *grow, float *stage
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const float t = __builtin_fmaf(v[u], gh[s[u]], 0.f);
-                    acc[u] = lok ? t : 0.f;  // an idle lane's clamped slot contributes nothing
+                    // an idle lane's clamped slot contributes nothing
+                    acc[u] = lane_tree<KG, Sum>(sl.ok ? t : 0.f);
                 }
                 leave(h, base, acc);
             }
         } else {
             for (int h = 0; h < H; ++h) {
-                const float *gh = grow + h * DS;
                 float acc[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) acc[u] = 0.f;
-                for (int lb = 0; lb < k; lb += KG) {
-                    const int l = lb + l0;
-                    const bool lok = l < k;
-                    const uint32_t lc = (uint32_t)(lok ? l : k - 1);
-                    const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
-                    float v[U];
-                    int s[U];
-#pragma unroll
-                    for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const float t = __builtin_fmaf(v[u], gh[min(s[u], trash)], acc[u]);
-                        acc[u] = lok ? t : acc[u];
-                    }
-                }
+                record_dots<KG, U>(rrs, RS, c, grow + h * DS, k, trash, l0, acc);
                 leave(h, base, acc);
             }
         }
@@ -307,27 +234,17 @@ __global__ __launch_bounds__(kBlock) void edge_grad_heads_kernel(
         if (lane < DS - D) grow[h * DS + D + lane] = 0.f;
 
     const ItemRange it = item_range(row_ptr, num_rows, num_e, item, chunk);
-    int q = it.r - 1;
-    RowPiece p{0, 0, false};
-    if (it.r > 0) p = cont_piece(CutAtEnd{}, it.p_lo, it.d1, it.r, row_ptr[it.r]);
-    for (;;) {
-        const int64_t sb = p.sb, se = p.se;
-        if (q >= 0 && sb < se) {
-            const float div = row_div ? row_div[q] : 1.f;  // loaded before the walk
-            wave_lds_fence();  // the previous piece's reads of grow are done
-            for (int h = 0; h < H; ++h)
-                stage_row(grow + h * DS, grad_out + ((int64_t)h * num_rows + q) * D, D, vec != 0,
-                          lane);
-            wave_lds_fence();
-            walk_piece_heads<KG, U>(grow, stage, col_idx, rec, RS, grad_edge, num_e, H, DS,
-                                    (int)sb, (int)se, k, DS - 1, div, row_div != nullptr, lane);
-        }
-        ++q;
-        if (q >= num_rows) break;
-        const int64_t rb = row_ptr[q];
-        if (!row_owned(it.d1, q, rb)) break;  // row q's token belongs to a later item
-        p = row_piece(CutAtEnd{}, it.d1, q, rb, row_ptr[q + 1]);
-    }
+    walk_cut_item(row_ptr, num_rows, it, [&](int q, int64_t sb, int64_t se, int64_t, bool) {
+        if (sb >= se) return;
+        const float div = row_div ? row_div[q] : 1.f;  // loaded before the walk
+        wave_lds_fence();  // the previous piece's reads of grow are done
+        for (int h = 0; h < H; ++h)
+            stage_row(grow + h * DS, grad_out + ((int64_t)h * num_rows + q) * D, D, vec != 0,
+                      lane);
+        wave_lds_fence();
+        walk_piece_heads<KG, U>(grow, stage, col_idx, rec, RS, grad_edge, num_e, H, DS, (int)sb,
+                                (int)se, k, DS - 1, div, row_div != nullptr, lane);
+    });
 }
 
 // Waves one CU holds at once: 8 per SIMD by VGPRs (at most 64, the kernel-resource-usage

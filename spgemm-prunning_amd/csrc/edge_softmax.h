@@ -28,8 +28,9 @@ struct Sum {
 struct Max {  // fmaxf drops a NaN operand: the sums carry it
     static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); }
 };
-// Op over each aligned group of KG lanes (8 or 64), left in every lane of the group: the fixed
-// butterfly of edge_grad.hip's group_sum, both lanes of a pair combining the same two numbers.
+// Op over each aligned group of KG lanes (8 .. 64), left in every lane of the group: a butterfly
+// of fixed shape, both lanes of a pair combining the same two numbers, so the group agrees bitwise
+// and the order is the same every run.
 template <int KG, class Op>
 __device__ __forceinline__ float lane_tree(float x) {
     x = Op::f(x, dpp_f<0xB1>(x));   // quad_perm [1,0,3,2]
@@ -562,7 +563,8 @@ inline SlotLayout slot_layout(int64_t n, int64_t num_e, int chunk, size_t base) 
 }
 inline dim3 slot_grid(int n_items) { return dim3((unsigned)ceil_div(2 * (int64_t)n_items, kBlock)); }
 
-int check_sizes(int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t chunk_edges) {
+// inline, as check_slope and check_workspace: not every unit that includes this has such an entry
+inline int check_sizes(int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t chunk_edges) {
     MAXK_REQUIRE(num_rows >= 0 && num_rows < (1LL << 31), "num_rows out of range: %lld",
                  (long long)num_rows);
     MAXK_REQUIRE(num_cols >= 0 && num_cols < (1LL << 31), "num_cols out of range: %lld",
@@ -571,12 +573,12 @@ int check_sizes(int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t chunk
     MAXK_REQUIRE(chunk_edges >= 0, "chunk_edges must be >= 0");
     return MAXK_OK;
 }
-inline int check_slope(float slope) {  // inline: the dot-product attention has no slope
+inline int check_slope(float slope) {
     MAXK_REQUIRE(slope >= 0.f && slope <= 1.f, "negative_slope must be in [0, 1], got %g",
                  (double)slope);  // a NaN fails both comparisons
     return MAXK_OK;
 }
-int check_workspace(const void *workspace, size_t bytes, size_t need) {
+inline int check_workspace(const void *workspace, size_t bytes, size_t need) {
     MAXK_REQUIRE(workspace && bytes >= need, "workspace too small: need %zu bytes, got %zu", need,
                  workspace ? bytes : (size_t)0);
     MAXK_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-B aligned");

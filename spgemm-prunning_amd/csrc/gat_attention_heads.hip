@@ -106,15 +106,8 @@ struct WeightLane {
 // head's score ss[c * HP + head]; returns the lane's sum of p (the same in every lane of a
 // group).  active: the group has an edge slot and a head in this pass; else it writes its trash
 // column only.  POISON: p = NaN and nothing is summed (the rows whose z is no positive number).
-// DROP (attn_dropout.h): a wave step holds EP * U edges and the pass's heads lie in dp.qp <= 2
-// quads, so one Philox evaluation per lane -- lane t on the edge at offset t % span of the next
-// S = 64 / (EP * U * qp) steps (span = S * EP * U; its CSR position is sb + its index in the
-// piece) and the quad dp.q0 + t / span -- serves S steps: four ballots, one per head of a quad,
-// carry the bits, and each group keeps its head's 64 (`mine`).  The sum of p takes the unmasked
-// weights and the products p * (0 or 1): a dropped NaN or Inf stays NaN.
-struct DropPass {
-    int q0, qp, head;  // the pass's first quad of heads and their number; the group's head
-};
+// DROP: the pass mask of attn_dropout.h (PassMask) multiplied into the products; the sum of p
+// takes the unmasked weights.
 template <int KG, int HP, int U, bool POISON, bool DROP>
 __device__ __forceinline__ float walk_attn(float *acc_g, const int32_t *__restrict__ col_idx,
                                            const float *__restrict__ ss, const WeightLane &wl,
@@ -128,14 +121,7 @@ __device__ __forceinline__ float walk_attn(float *acc_g, const int32_t *__restri
     const auto crs = wave_buffer(col_idx + sb, (uint32_t)n * 4u);
     const auto rrs = wave_buffer(rec, 0xffffffffu);  // offsets < num_cols * RS < 2^32
     float ps = 0.f;
-    const int EU = EP * U;
-    int S = 1, span_log = 0, js = 0, qsel = 0;
-    uint64_t mine = 0;
-    if constexpr (DROP) {
-        S = kWave / (EU * dp.qp);  // powers of two, EU * qp <= 64
-        span_log = 31 - __clz(S * EU);
-        qsel = min(max((dp.head >> 2) - dp.q0, 0), dp.qp - 1);
-    }
+    PassMask<DROP> pm(dp, EP * U);
     for (int base = 0; base < n; base += EP * U) {
         int c[U];
         float w[U];
@@ -154,24 +140,14 @@ __device__ __forceinline__ float walk_attn(float *acc_g, const int32_t *__restri
             const int ct = (int)__builtin_amdgcn_raw_buffer_load_b32(crs, it * 4, 0, 0);
             const float x = ss[(uint32_t)ct * (uint32_t)HP + (uint32_t)wl.head];
             const float pt = wl.on && it < n ? expf(leaky(wl.sdh + x, slope) - wl.shift) : 0.f;
-            if constexpr (DROP) {
-                if (js == 0) {  // wave-uniform: the masks of this and the next S - 1 steps
-                    const uint32_t bits =
-                        drop_bits(dm, (uint32_t)(sb + base + (lane & ((1 << span_log) - 1))),
-                                  (uint32_t)(dp.q0 + (lane >> span_log)));
-                    const uint64_t b0 = __ballot(bits & 1u), b1 = __ballot(bits & 2u),
-                                   b2 = __ballot(bits & 4u), b3 = __ballot(bits & 8u);
-                    const int hb = dp.head & 3;
-                    mine = (hb == 0 ? b0 : hb == 1 ? b1 : hb == 2 ? b2 : b3) >> (qsel << span_log);
-                }
-            }
+            pm.refresh(dm, dp, sb + base, lane);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 w[u] = __shfl(pt, u * G + grp);
                 ps += w[u];
-                if constexpr (DROP) w[u] *= (mine >> (js * EU + u * EP + eg)) & 1 ? 0.f : 1.f;
+                if constexpr (DROP) w[u] *= pm.keep(u * EP + eg);
             }
-            if constexpr (DROP) js = js + 1 == S ? 0 : js + 1;
+            pm.next();
         }
         scatter_records<KG, U>(acc_g, rrs, RS, k, trash, l0, c, w, active, base, EP, eg, n);
     }
@@ -245,8 +221,7 @@ __global__ __launch_bounds__(kBlock, HP == 8 ? 4 : 5) void gath_fwd_kernel(
             if (n > 0)
                 ps = walk_attn<KG, HP, U, false, DROP>(
                     g.acc_g, col_idx, ss, wl, slope, rec, RS, (int)sb, (int)se, k, DS - 1, g.EP,
-                    g.eg, active, lane, dm,
-                    DropPass{h0 >> 2, ((min(h0 + HC, H) - 1) >> 2) - (h0 >> 2) + 1, head});
+                    g.eg, active, lane, dm, drop_pass(h0, HC, H, head));
             const int bad = bad_heads<KG>(ps, g.EP, HC, h0, H);
             if (whole && n > 0 && bad) {  // rare: NaN wherever such a head's row has an addend
                 wave_lds_fence();
@@ -447,23 +422,11 @@ int attention_heads(const int32_t *row_ptr, const int32_t *col_idx, const float 
                      ((uintptr_t)s_src & 3) == 0 && ((uintptr_t)out & 3) == 0 &&
                      ((uintptr_t)row_max & 3) == 0 && ((uintptr_t)row_sum & 3) == 0,
                  "float buffers must be 4-B aligned");
-#define MAXK_GATH_FWD(HP, DROP, DM)                                                             \
-    launch_attention<HP, DROP>(row_ptr, col_idx, s_dst, s_src, negative_slope, cbsr_val,        \
-                               cbsr_idx, out, row_max, row_sum, num_rows, num_cols, num_e, D, k, \
-                               H, L, workspace, s, DM)
-    if (dm) {
-        switch (L.hp) {
-            case 2: return MAXK_GATH_FWD(2, true, *dm);
-            case 4: return MAXK_GATH_FWD(4, true, *dm);
-            default: return MAXK_GATH_FWD(8, true, *dm);
-        }
-    }
-    switch (L.hp) {
-        case 2: return MAXK_GATH_FWD(2, false, NoMask{});
-        case 4: return MAXK_GATH_FWD(4, false, NoMask{});
-        default: return MAXK_GATH_FWD(8, false, NoMask{});
-    }
-#undef MAXK_GATH_FWD
+    return with_heads_mask(L.hp, dm, [&](auto hp_c, const auto &mask) {
+        return launch_attention<decltype(hp_c)::value, is_drop_v<decltype(mask)>>(
+            row_ptr, col_idx, s_dst, s_src, negative_slope, cbsr_val, cbsr_idx, out, row_max,
+            row_sum, num_rows, num_cols, num_e, D, k, H, L, workspace, s, mask);
+    });
 }
 }  // namespace
 
@@ -495,13 +458,11 @@ extern "C" int maxk_gat_attention_heads_dropout(
     int32_t dim_origin, int32_t dim_k, int32_t num_heads, int32_t chunk_edges, float p,
     uint64_t seed, void *workspace, size_t workspace_bytes, void *stream) {
     clear_error();
-    if (int rc = check_dropout(p)) return rc;
-    // p == 0 drops nothing and scales by 1: the kernels of the entry without dropout
-    const DropMask dm = drop_mask(p, seed);
-    return attention_heads(row_ptr, col_idx, s_dst, s_src, negative_slope, cbsr_val, cbsr_idx, out,
-                           row_max, row_sum, num_rows, num_cols, num_e, dim_origin, dim_k,
-                           num_heads, chunk_edges, workspace, workspace_bytes, stream,
-                           p > 0.f ? &dm : nullptr);
+    return with_dropout(p, seed, [&](const DropMask *dm) {
+        return attention_heads(row_ptr, col_idx, s_dst, s_src, negative_slope, cbsr_val, cbsr_idx,
+                               out, row_max, row_sum, num_rows, num_cols, num_e, dim_origin, dim_k,
+                               num_heads, chunk_edges, workspace, workspace_bytes, stream, dm);
+    });
 }
 
 extern "C" size_t maxk_gat_edge_alpha_heads_workspace_size(int32_t num_heads, int64_t num_rows,

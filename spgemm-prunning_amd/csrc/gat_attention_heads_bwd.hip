@@ -14,9 +14,9 @@
 // touches an edge, so a row cut over items needs no second walk.
 //
 //  1. launch_cbsr_pack and esmh_interleave_kernel fill the workspace's records and ss_t.
-//  2. gath_bwd_kernel, one wavefront per item of `chunk` tokens cut at the item's end
-//     (CutAtEnd, the partition of edge_grad_heads_kernel and esmh_bwd_kernel), KG = pow2ceil(k)
-//     lanes per edge (8 .. 64), G = 64 / KG edges per wave step, U steps in flight.
+//  2. gath_bwd_kernel, a staged-row walk (piece_walk.h): one wavefront per item of `chunk` tokens
+//     cut at the item's end (CutAtEnd), KG = pow2ceil(k) lanes per edge (8 .. 64), G = 64 / KG
+//     edges per wave step, U steps in flight.
 //     * per row piece: the H rows grad_out[h, r, :] staged side by side in the wave's LDS
 //       (H * DS floats, the pad columns [D, DS) zero), out[h, r, :] streamed beside them, and
 //       t_h reduced by the fixed 64-lane butterfly: the same number in every item holding a
@@ -50,7 +50,7 @@
 
 #include "attn_dropout.h"
 #include "edge_softmax.h"
-#include "heads_walk.h"  // the host side's record geometry
+#include "piece_walk.h"
 #include "sspmm_bwd.h"
 
 // Wave steps of record loads in flight.  4: 97 to 122 VGPRs over the twelve instantiations (four
@@ -63,31 +63,6 @@
 namespace maxk {
 namespace {
 
-// grow[0:D] = g[0:D]; returns this lane's part of sum_{j : o[j] != 0} o[j] * g[j].  One wave.
-__device__ __forceinline__ float stage_dot(float *grow, const float *__restrict__ g,
-                                           const float *__restrict__ o, int D, bool vec,
-                                           int lane) {
-    float t = 0.f;
-    if (vec) {
-        for (int j = lane * 4; j < D; j += kWave * 4) {
-            const float4 gv = *reinterpret_cast<const float4 *>(&g[j]);
-            const float4 ov = *reinterpret_cast<const float4 *>(&o[j]);
-            *reinterpret_cast<float4 *>(&grow[j]) = gv;
-            t = ov.x != 0.f ? __builtin_fmaf(ov.x, gv.x, t) : t;
-            t = ov.y != 0.f ? __builtin_fmaf(ov.y, gv.y, t) : t;
-            t = ov.z != 0.f ? __builtin_fmaf(ov.z, gv.z, t) : t;
-            t = ov.w != 0.f ? __builtin_fmaf(ov.w, gv.w, t) : t;
-        }
-    } else {
-        for (int j = lane; j < D; j += kWave) {
-            const float gv = g[j], ov = o[j];
-            grow[j] = gv;
-            t = ov != 0.f ? __builtin_fmaf(ov, gv, t) : t;
-        }
-    }
-    return t;
-}
-
 // What lane h of a group holds of head h for the row being walked (pad heads: 0, 0, 1, 0).
 struct HeadLane {
     float sd, shift, sum, t;
@@ -95,10 +70,9 @@ struct HeadLane {
 
 // The edges [sb, se) (sb < se) of one row whose grad_out rows are staged in grow: stores their
 // T rows and gzT vectors; returns this lane's sum of the gz of head lane % KG over its group's
-// edges (lanes % KG >= H: 0).  DROP (attn_dropout.h): lane j < U * QP of a group evaluates the
-// mask of the group's edge j % U for the quad of heads j / U, QP = ceil(HP / 4) quads; lane h
-// fetches its head's bit with one shuffle per edge and keeps d = 0 or scale beside alpha:
-// T gains alpha * d * x and gz = alpha * (d * ga - t), t from the dropped out.
+// edges (lanes % KG >= H: 0).  DROP: lane h takes its head's bits of the step from step_gone
+// (attn_dropout.h) and keeps d = 0 or scale beside alpha: T gains alpha * d * x and
+// gz = alpha * (d * ga - t), t from the dropped out.
 template <int KG, int HP, int U, bool DROP>
 __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
                                                 const int32_t *__restrict__ col_idx,
@@ -141,18 +115,8 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
                 pos |= (z > 0.f ? 1u : 0u) << u;
             }
         }
-        uint32_t gone = 0u;  // DROP, lane h: bit u, head h of the group's edge u is dropped
-        if constexpr (DROP) {
-            constexpr int QP = (HP + 3) / 4;
-            static_assert(U * QP <= KG, "a group evaluates its step's masks in one round");
-            const uint32_t bits = drop_bits(
-                dm, (uint32_t)(sb + base + (l0 % U) * G + grp), (uint32_t)((l0 / U) % QP));
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t b = __shfl(bits, lane0 + ((l0 >> 2) % QP) * U + u);
-                gone |= ((b >> (l0 & 3)) & 1u) << u;
-            }
-        }
+        // DROP, lane h: bit u, head h of the group's edge u is dropped
+        const uint32_t gone = step_gone<KG, HP, U, DROP>(dm, sb + base, grp, l0, lane0);
         auto dk = [&](int u) {  // the mask factor d
             if constexpr (DROP) return (gone >> u) & 1u ? 0.f : dm.scale;
             else return 1.f;
@@ -171,20 +135,13 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
 #pragma unroll
         for (int u = 0; u < U; ++u) ga[u] = 0.f;
         if (k <= KG) {  // one slot per lane: the record is loaded once for all heads
-            const bool lok = l0 < k;
-            const uint32_t lc = (uint32_t)(lok ? l0 : k - 1);
-            const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+            const RecordSlot sl(l0, k);
+            const PackedSrc src = sl.src(rrs, k, RS);
             float v[U];
             int s[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
-            uint32_t keep = 0u;  // bit u: the slot carries a (folded) value under a selector < D
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                keep |= (lok && s[u] < 0x100 ? 1u : 0u) << u;
-                const int raw = s[u] & 255;  // the caller's selector
-                s[u] = raw < D ? raw : trash;
-            }
+            const uint32_t keep = caller_columns(s, sl.ok, D, trash);
             float tc[U];
 #pragma unroll
             for (int h = 0; h < HP; ++h) {
@@ -201,11 +158,7 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
                     }
                 }
             }
-#pragma unroll
-            for (int u = 0; u < U; ++u)  // idle lanes and edges past the piece's end: dropped
-                __builtin_amdgcn_raw_buffer_store_b32(
-                    __float_as_uint(tc[u]), trs,
-                    lok ? ((base + u * G + grp) * k + l0) * 4 : (int)0x80000000, 0, MAXK_T_AUX);
+            store_t_rows<KG, U>(trs, tc, sl.ok, base, grp, k, l0);
         } else {  // k > 64 (KG == 64, one edge per wave step): passes over l
 #pragma unroll
             for (int h = 0; h < HP; ++h) {
@@ -215,18 +168,15 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
 #pragma unroll
                     for (int u = 0; u < U; ++u) acc[u] = 0.f;
                     for (int lb = 0; lb < k; lb += KG) {
-                        const int l = lb + l0;
-                        const bool lok = l < k;
-                        const uint32_t lc = (uint32_t)(lok ? l : k - 1);
-                        const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc,
-                                            (uint32_t)RS};
+                        const RecordSlot sl(lb + l0, k);
+                        const PackedSrc src = sl.src(rrs, k, RS);
                         float v[U];
                         int s[U];
 #pragma unroll
                         for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
 #pragma unroll
                         for (int u = 0; u < U; ++u) {
-                            const bool keep = lok && s[u] < 0x100;
+                            const bool keep = sl.ok && s[u] < 0x100;
                             const float x = gh[min(s[u], trash)];
                             acc[u] = keep ? __builtin_fmaf(v[u], x, acc[u]) : acc[u];
                         }
@@ -239,19 +189,13 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
                 }
             }
             for (int lb = 0; lb < k; lb += KG) {
-                const int l = lb + l0;
-                const bool lok = l < k;
-                const uint32_t lc = (uint32_t)(lok ? l : k - 1);
-                const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+                const RecordSlot sl(lb + l0, k);
+                const PackedSrc src = sl.src(rrs, k, RS);
                 float v[U], tc[U];
                 int s[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int raw = s[u] & 255;
-                    s[u] = raw < D ? raw : trash;
-                }
+                caller_columns(s, sl.ok, D, trash);
 #pragma unroll
                 for (int h = 0; h < HP; ++h) {
                     if (h < H) {
@@ -264,12 +208,7 @@ __device__ __forceinline__ float walk_piece_bwd(const float *grow, int DS,
                         }
                     }
                 }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    __builtin_amdgcn_raw_buffer_store_b32(
-                        __float_as_uint(tc[u]), trs,
-                        lok ? ((base + u * G + grp) * k + l) * 4 : (int)0x80000000, 0,
-                        MAXK_T_AUX);
+                store_t_rows<KG, U>(trs, tc, sl.ok, base, grp, k, lb + l0);
             }
         }
         // lane h: gz of head h (a pad head: 0 * (0 - 0)), one vector per edge from the HP lanes
@@ -376,8 +315,6 @@ __global__ __launch_bounds__(kBlock, DROP ? 4 : 1) void gath_bwd_kernel(
     }
 }
 
-// A piece's T rows are addressed through a descriptor of 4 * k * n bytes with 32-bit offsets.
-constexpr int kBwdMaxChunk = 1 << 20;
 // Resident waves per CU the items are sized for: four per SIMD by VGPRs, fewer where the staged
 // rows fill the LDS first.
 constexpr int kBwdResident = 16;
@@ -396,9 +333,7 @@ BwdLayout bwd_layout(int64_t num_rows, int64_t num_cols, int64_t num_e, int D, i
     BwdLayout L{record_geom(num_cols, D, k)};
     L.hp = hp_of(H);
     const size_t per_block = (size_t)kWavesPerBlock * H * L.DS * sizeof(float);
-    const int by_lds = (int)(kPullLdsBytes / per_block) * kWavesPerBlock;
-    L.chunk = fwd_chunk(num_rows, num_e, chunk, by_lds < kBwdResident ? by_lds : kBwdResident);
-    if (L.chunk > kBwdMaxChunk) L.chunk = kBwdMaxChunk;
+    L.chunk = walk_chunk(num_rows, num_e, chunk, per_block, kBwdResident, kBwdMaxChunk);
     L.n_items = token_items(num_rows, num_e, L.chunk);
     const int64_t cap = item_cap(num_rows + num_e, chunk, L.n_items);
     const size_t part = al256((size_t)cap * 2 * sizeof(float));
@@ -513,24 +448,12 @@ int attention_heads_backward(
                      ((uintptr_t)grad_out & 3) == 0 && ((uintptr_t)grad_s_dst & 3) == 0 &&
                      ((uintptr_t)grad_s_src & 3) == 0 && ((uintptr_t)grad_cbsr & 3) == 0,
                  "float buffers must be 4-B aligned");
-#define MAXK_GATH_BWD(HP, DROP, DM)                                                             \
-    launch_attention_bwd<HP, DROP>(row_ptr, col_idx, col_ptr, csc_eid, s_dst, s_src,            \
-                                   negative_slope, cbsr_val, cbsr_idx, out, row_max, row_sum,   \
-                                   grad_out, grad_s_dst, grad_s_src, grad_cbsr, num_rows,       \
-                                   num_cols, num_e, D, k, H, chunk_edges, L, workspace, s, DM)
-    if (dm) {
-        switch (L.hp) {
-            case 2: return MAXK_GATH_BWD(2, true, *dm);
-            case 4: return MAXK_GATH_BWD(4, true, *dm);
-            default: return MAXK_GATH_BWD(8, true, *dm);
-        }
-    }
-    switch (L.hp) {
-        case 2: return MAXK_GATH_BWD(2, false, NoMask{});
-        case 4: return MAXK_GATH_BWD(4, false, NoMask{});
-        default: return MAXK_GATH_BWD(8, false, NoMask{});
-    }
-#undef MAXK_GATH_BWD
+    return with_heads_mask(L.hp, dm, [&](auto hp_c, const auto &mask) {
+        return launch_attention_bwd<decltype(hp_c)::value, is_drop_v<decltype(mask)>>(
+            row_ptr, col_idx, col_ptr, csc_eid, s_dst, s_src, negative_slope, cbsr_val, cbsr_idx,
+            out, row_max, row_sum, grad_out, grad_s_dst, grad_s_src, grad_cbsr, num_rows, num_cols,
+            num_e, D, k, H, chunk_edges, L, workspace, s, mask);
+    });
 }
 }  // namespace
 
@@ -566,13 +489,11 @@ extern "C" int maxk_gat_attention_heads_dropout_backward(
     int32_t dim_k, int32_t num_heads, int32_t chunk_edges, float p, uint64_t seed,
     void *workspace, size_t workspace_bytes, void *stream) {
     clear_error();
-    if (int rc = check_dropout(p)) return rc;
-    // p == 0 drops nothing and scales by 1: the kernels of the entry without dropout
-    const DropMask dm = drop_mask(p, seed);
-    return attention_heads_backward(row_ptr, col_idx, col_ptr, csc_eid, s_dst, s_src, negative_slope,
-                                    cbsr_val, cbsr_idx, out, row_max, row_sum, grad_out,
-                                    grad_s_dst, grad_s_src, grad_cbsr, num_rows, num_cols, num_e,
-                                    dim_origin, dim_k, num_heads, chunk_edges, workspace,
-                                    workspace_bytes, stream,
-                                    p > 0.f ? &dm : nullptr);
+    return with_dropout(p, seed, [&](const DropMask *dm) {
+        return attention_heads_backward(row_ptr, col_idx, col_ptr, csc_eid, s_dst, s_src,
+                                        negative_slope, cbsr_val, cbsr_idx, out, row_max, row_sum,
+                                        grad_out, grad_s_dst, grad_s_src, grad_cbsr, num_rows,
+                                        num_cols, num_e, dim_origin, dim_k, num_heads, chunk_edges,
+                                        workspace, workspace_bytes, stream, dm);
+    });
 }

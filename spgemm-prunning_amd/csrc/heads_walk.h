@@ -78,17 +78,15 @@ __device__ __forceinline__ void scatter_records(float *acc_g, const __amdgpu_buf
                                                 const int (&c)[U], const float (&w)[U],
                                                 bool active, int base, int EP, int eg, int n) {
     for (int lb = 0; lb < k; lb += KG) {
-        const int l = lb + l0;
-        const bool lok = l < k;
-        const uint32_t lc = (uint32_t)(lok ? l : k - 1);
-        const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+        const RecordSlot sl(lb + l0, k);
+        const PackedSrc src = sl.src(rrs, k, RS);
         float v[U];
         int s[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const bool live = lok && active && base + u * EP + eg < n;
+            const bool live = sl.ok && active && base + u * EP + eg < n;
             float *a = &acc_g[live ? min(s[u], trash) : trash];
             *a = __builtin_fmaf(w[u], v[u], *a);
         }
@@ -165,6 +163,7 @@ __device__ __forceinline__ int bad_heads(float ps, int EP, int HC, int h0, int H
         if (!(pass_z<KG>(ps, j, EP, HC) > 0.f)) bad |= 1 << j;
     return bad;
 }
+
 // The item driver: piece(row, sb, se, whole, owned) for the edges [sb, se) of every row the item
 // walks.  First the continuation of row r - 1 (its token precedes the item): only a hub row
 // leaves one (owned = false: it goes to the item's slab), and slab_row[item] names it for the
@@ -283,12 +282,12 @@ inline int heads_per_pass(int H, int kg) {
 }
 
 // The item size of a walk whose workgroups take lds_per_block bytes: sized for the waves a CU
-// holds, by_regs by VGPRs, fewer when the LDS fills the CU first.
+// holds, by_regs by VGPRs, fewer when the LDS fills the CU first; at most cap tokens.
 inline int walk_chunk(int64_t num_rows, int64_t num_e, int chunk, size_t lds_per_block,
-                      int by_regs) {
+                      int by_regs, int cap = kMaxChunk) {
     const int by_lds = (int)(kPullLdsBytes / lds_per_block) * kWavesPerBlock;
     const int c = fwd_chunk(num_rows, num_e, chunk, by_lds < by_regs ? by_lds : by_regs);
-    return c > kMaxChunk ? kMaxChunk : c;
+    return c > cap ? cap : c;
 }
 
 // The per-item parts of a workspace from `base` on, for `cap` items: the slabs [H, cap, D], with

@@ -187,18 +187,13 @@ struct EdgeWalker {
             }
             for (int lb = 0; lb < k; lb += KG) {
                 const int l = lb + l0;
-                const bool lok = l < k;
-                const uint32_t lc = (uint32_t)(lok ? l : k - 1);
-                const uint32_t vo = 4u * lc, so = 4u * (uint32_t)k + 2u * lc;
+                const RecordSlot slot(l, k);
+                const bool lok = slot.ok;
+                const PackedSrc src = slot.src(rrs, k, RS);
                 float v[U];
                 int s[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const uint32_t ro = __umul24((uint32_t)c[u], (uint32_t)RS);
-                    v[u] = __uint_as_float(
-                        __builtin_amdgcn_raw_buffer_load_b32(rrs, (int)(ro + vo), 0, 0));
-                    s[u] = __builtin_amdgcn_raw_buffer_load_b16(rrs, (int)(ro + so), 0, 0);
-                }
+                for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const bool live = lok && it * U + u < len_g;
@@ -255,18 +250,13 @@ struct EdgeWalker {
                 }
                 for (int lb = 0; lb < k; lb += KG) {  // one pass unless k > 64
                     const int l = lb + l0;
-                    const bool lok = l < k;
-                    const uint32_t lc = (uint32_t)(lok ? l : k - 1);
-                    const uint32_t vo = 4u * lc, so = 4u * (uint32_t)k + 2u * lc;
+                    const RecordSlot slot(l, k);
+                    const bool lok = slot.ok;
+                    const PackedSrc src = slot.src(rrs, k, RS);
                     float v[U];
                     int s[U];
 #pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const uint32_t ro = __umul24((uint32_t)c[u], (uint32_t)RS);
-                        v[u] = __uint_as_float(
-                            __builtin_amdgcn_raw_buffer_load_b32(rrs, (int)(ro + vo), 0, 0));
-                        s[u] = __builtin_amdgcn_raw_buffer_load_b16(rrs, (int)(ro + so), 0, 0);
-                    }
+                    for (int u = 0; u < U; ++u) src.load(c[u], v[u], s[u]);
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const bool live = lok && base + u * G + grp < n;
@@ -611,9 +601,8 @@ __global__ __launch_bounds__(kBlock, EMIT ? MAXK_FWD_EMIT_WAVES : MAXK_FWD_WAVES
                                        rec_src(), row_div, out, D, k, DS - 1, lane, accumulate,
                                        min(MAXK_FWD_STREAM, chunk), num_e);
             } else {
-                const uint32_t lc = (uint32_t)(lok_s ? lane % KG : k - 1);
-                const PackedSrc src{wave_buffer(rec, 0xffffffffu), 4u * lc,
-                                    4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+                const PackedSrc src =
+                    RecordSlot(lane % KG, k).src(wave_buffer(rec, 0xffffffffu), k, RS);
                 r = stream_rows<KG, U>(acc, DS, r, row_ptr, num_rows, d1, col_idx, edge_val, src,
                                        row_div, out, D, k, DS - 1, lane, accumulate,
                                        min(MAXK_FWD_STREAM, chunk), num_e);

@@ -105,10 +105,9 @@ __global__ __launch_bounds__(kBlock) void max_fwd_kernel(
                 c[u] = ei < n ? col_idx[e[u]] : 0;
             }
             for (int lb = 0; lb < k; lb += KG) {
-                const int l = lb + l0;
-                const bool lok = l < k;
-                const uint32_t lc = (uint32_t)(lok ? l : k - 1);
-                const PackedSrc src{rrs, 4u * lc, 4u * (uint32_t)k + 2u * lc, (uint32_t)RS};
+                const RecordSlot slot(lb + l0, k);
+                const bool lok = slot.ok;
+                const PackedSrc src = slot.src(rrs, k, RS);
                 float v[kMaxU];
                 int s[kMaxU];
 #pragma unroll

@@ -15,9 +15,10 @@
 //               fixup -- in every later item it reaches.  An item then walks at most
 //               2 * chunk tokens (the forward, both dense-route walks).
 //
-// The first part (item count, cut rules) is plain C++17 over integers and touches no memory:
-// tests/partition_check.cpp includes this header alone and checks the rules on the CPU.  The
-// device part (item range, pointer window, row hand-out) is compiled by hipcc only.
+// The first part (item count, cut rules, the CutAtEnd item driver) is plain C++17 over integers
+// and reads nothing but the pointer array: tests/partition_check.cpp includes this header alone
+// and checks the rules, through the driver the kernels run, on the CPU.  The device part (item
+// range, pointer window, row hand-out) is compiled by hipcc only.
 #pragma once
 
 #include <cstdint>
@@ -82,6 +83,42 @@ MAXK_HD RowPiece row_piece(CutHubRows, int64_t d1, int q, int64_t rb, int64_t re
     return {rb, hub && d1 - q - 1 < re ? d1 - q - 1 : re, hub};
 }
 
+// An item's tokens [d0, d1), its first owned row r (n when it owns none) and its first edge
+// p_lo = d0 - r: the tokens before d0 hold r rows (item_range builds it on the device).
+struct ItemRange {
+    int64_t d0, d1;
+    int r;
+    int64_t p_lo;
+};
+
+// The CutAtEnd item driver: piece(q, sb, se, re, cont) for the edges [sb, se) of every row the
+// item `it` of ptr[0..n] walks, re the row's end.  First the continuation of row r - 1 (cont: its
+// token precedes the item), then the rows whose token the item holds, the last one cut at d1.
+// Every piece is reported through one call site, so a walk is the same instructions for a
+// continuation and an owned row; an empty piece is reported too (an owned row without edges has
+// sb == re), and a caller with nothing to do for one skips it.  se == re: the piece ends its row.
+template <class Piece>
+MAXK_HD void walk_cut_item(const int32_t *ptr, int n, const ItemRange &it, Piece &&piece) {
+    int q = it.r - 1;
+    bool cont = true;
+    int64_t re = 0;
+    RowPiece p{0, 0, false};
+    if (it.r > 0) {
+        re = ptr[it.r];
+        p = cont_piece(CutAtEnd{}, it.p_lo, it.d1, it.r, re);
+    }
+    for (;;) {
+        if (q >= 0) piece(q, p.sb, p.se, re, cont);
+        cont = false;
+        ++q;
+        if (q >= n) break;
+        const int64_t rb = ptr[q];
+        if (!row_owned(it.d1, q, rb)) break;  // row q's token belongs to a later item
+        re = ptr[q + 1];
+        p = row_piece(CutAtEnd{}, it.d1, q, rb, re);
+    }
+}
+
 #if defined(__HIPCC__)
 
 // Returns the first r in [0, n] whose token is >= d (ptr[n] + n >= d required).  64-ary search
@@ -111,13 +148,7 @@ __device__ __forceinline__ int wave_first_row_token(const int32_t *__restrict__ 
     return r > hi ? hi : r;
 }
 
-// An item's tokens [d0, d1), its first owned row r (n when it owns none) and its first edge
-// p_lo = d0 - r: the tokens before d0 hold r rows.  One wave; every member is wave-uniform.
-struct ItemRange {
-    int64_t d0, d1;
-    int r;
-    int64_t p_lo;
-};
+// One wave; every member of the result is wave-uniform.
 __device__ __forceinline__ ItemRange item_range(const int32_t *__restrict__ ptr, int n,
                                                 int64_t num_e, int item, int chunk) {
     const int64_t total = (int64_t)n + num_e;

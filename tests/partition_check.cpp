@@ -1,6 +1,7 @@
 // The cut rules of csrc/token_items.h, checked on the CPU: this program includes that header
 // alone (plain C++17, no HIP), walks every item of a set of pointer arrays the way the kernels
-// do -- a plain binary search for the item's first row, then the header's cont_piece /
+// do -- a plain binary search for the item's first row, then under CutAtEnd the header's item
+// driver walk_cut_item, the function the kernels run, and under CutHubRows its cont_piece /
 // row_piece -- and compares who walks which edge with the rules' definition on the tokens.
 //
 //   partition_check [FILE...]   each FILE: one more pointer array, whitespace-separated
@@ -76,39 +77,49 @@ static Walk walk(const Ptr &ptr, int chunk, const char *what) {
         const int64_t d0 = (int64_t)item * chunk;
         const int64_t d1 = std::min<int64_t>(d0 + chunk, total);
         const int r = first_row_token(ptr, n, d0);
-        const int64_t p_lo = d0 - r;
+        const ItemRange it{d0, d1, r, d0 - r};
+        auto own = [&](int q) {
+            CHECK(w.owner[(size_t)q] < 0, "%s chunk %d: row %d owned twice", what, chunk, q);
+            w.owner[(size_t)q] = item;
+            w.tokens[(size_t)item] += 1;
+        };
+        if constexpr (!HUBS) {  // the driver the kernels run
+            walk_cut_item(ptr.data(), n, it,
+                          [&](int q, int64_t sb, int64_t se, int64_t re, bool cont) {
+                const RowPiece p{sb, se, false};
+                CHECK(q >= 0 && q < n && cont == (q == r - 1) && re == ptr[q + 1],
+                      "%s chunk %d item %d: the driver reports row %d", what, chunk, item, q);
+                const RowPiece a = any_piece(CutAtEnd{}, d0, d1, q, ptr[q], ptr[q + 1]);
+                if (cont) {
+                    if (p.sb < p.se) {
+                        mark(item, p, q);
+                        w.slab_row[(size_t)item] = q;
+                    }
+                    CHECK((a.sb >= a.se && p.sb >= p.se) || (a.sb == p.sb && a.se == p.se),
+                          "%s chunk %d item %d: any_piece differs from cont_piece", what, chunk,
+                          item);
+                } else {
+                    own(q);
+                    CHECK(a.sb == p.sb && a.se == p.se, "%s chunk %d row %d: any_piece differs "
+                          "from row_piece", what, chunk, q);
+                    mark(item, p, q);
+                }
+            });
+            continue;
+        }
         if (r > 0) {
-            RowPiece p;
-            if constexpr (HUBS)
-                p = cont_piece(CutHubRows{}, p_lo, d1, r, ptr[r - 1], ptr[r], chunk);
-            else
-                p = cont_piece(CutAtEnd{}, p_lo, d1, r, ptr[r]);
-            if ((!HUBS || p.hub) && p.sb < p.se) {
+            const RowPiece p = cont_piece(CutHubRows{}, it.p_lo, d1, r, ptr[r - 1], ptr[r], chunk);
+            if (p.hub && p.sb < p.se) {
                 mark(item, p, r - 1);
                 w.slab_row[(size_t)item] = r - 1;
-            }
-            if constexpr (!HUBS) {
-                const RowPiece a = any_piece(CutAtEnd{}, d0, d1, r - 1, ptr[r - 1], ptr[r]);
-                CHECK((a.sb >= a.se && p.sb >= p.se) || (a.sb == p.sb && a.se == p.se),
-                      "%s chunk %d item %d: any_piece differs from cont_piece", what, chunk, item);
             }
         }
         for (int q = r; q < n; ++q) {
             if (!row_owned(d1, q, ptr[q])) break;
-            CHECK(w.owner[(size_t)q] < 0, "%s chunk %d: row %d owned twice", what, chunk, q);
-            w.owner[(size_t)q] = item;
-            w.tokens[(size_t)item] += 1;
-            RowPiece p;
-            if constexpr (HUBS) {
-                p = row_piece(CutHubRows{}, d1, q, ptr[q], ptr[q + 1], chunk);
-                CHECK(p.hub == (ptr[q + 1] - ptr[q] > chunk), "%s chunk %d row %d: hub flag", what,
-                      chunk, q);
-            } else {
-                p = row_piece(CutAtEnd{}, d1, q, ptr[q], ptr[q + 1]);
-                const RowPiece a = any_piece(CutAtEnd{}, d0, d1, q, ptr[q], ptr[q + 1]);
-                CHECK(a.sb == p.sb && a.se == p.se, "%s chunk %d row %d: any_piece differs from "
-                      "row_piece", what, chunk, q);
-            }
+            own(q);
+            const RowPiece p = row_piece(CutHubRows{}, d1, q, ptr[q], ptr[q + 1], chunk);
+            CHECK(p.hub == (ptr[q + 1] - ptr[q] > chunk), "%s chunk %d row %d: hub flag", what,
+                  chunk, q);
             mark(item, p, q);
         }
     }

@@ -9,7 +9,7 @@ Which kernels.  Every non-empty forward launches cbsr_pack_kernel or cbsr_pack4_
 (k % 4 == 0), dath_fwd_kernel<KG, 8> and softmax_fixup_kernel<false> (heads_walk.h, which also
 holds the walk the forward kernel shares with the other heads forwards); every non-empty alpha
 call the pack and dath_alpha_kernel<KG, 8>.  KG = 8 for k = 3, 7, 8, 16 for k = 16, 32 for k = 24, 32, 64 for
-k = 96 (k > KG: the several-slots-per-lane path of edge_logits and walk_dot).  The heads per pass
+k = 96 (k > KG: the several-slots-per-lane path of record_dots and walk_dot).  The heads per pass
 are HC = ceil(H / ceil(H / G)), G = 64 / KG: at H = 1, 2, 3, 5, 8 that is 1, 2, 3, 5, 8 (KG = 8),
 1, 2, 3, 3, 4 (KG = 16), 1, 2, 2, 2, 2 (KG = 32) and 1 (KG = 64), so test_parity, which runs
 every (k, H) of SHAPES x HEADS at the auto item size and at 64 tokens, reaches the four
