@@ -9,6 +9,7 @@ the 1-process HIP result (1e-5 relative: hub rows split differently over work it
 gradient partials are summed in another order) and against the oracle (1e-4, north_star).
 """
 import os
+import signal
 import socket
 import subprocess
 import sys
@@ -142,6 +143,29 @@ def test_sharded_forced_backward_modes(graph, single, bwd, stream, monkeypatch):
     _run_world(graph, single, 2, "gloo")
 
 
+def _kill_tree(pid):
+    """Kill `pid` and all its descendants.  The ranks of a self-launched bench are its
+    grandchildren, each in a session of its own (bench -> torch.distributed.run -> ranks):
+    killing the bench alone at the time limit left all of them on the GPU, and the next
+    test's ranks beside them were more processes than a GPU admits."""
+    kids = {}
+    for d in filter(str.isdigit, os.listdir("/proc")):
+        try:
+            with open(f"/proc/{d}/stat") as f:
+                kids.setdefault(int(f.read().rsplit(")", 1)[1].split()[1]), []).append(int(d))
+        except OSError:
+            pass
+    tree, todo = [], [pid]
+    while todo:
+        tree.append(todo.pop())
+        todo += kids.get(tree[-1], [])
+    for q in tree:
+        try:
+            os.kill(q, signal.SIGKILL)
+        except ProcessLookupError:
+            pass
+
+
 @pytest.mark.parametrize("graph,k,gpus,records", [("products", 32, 2, True),
                                                   ("products", 32, 4, True),
                                                   ("products", 32, 8, True),
@@ -163,18 +187,26 @@ def test_bench_self_launch(graph, k, gpus, records):
     env["MAXK_DIST_BACKEND"] = "gloo"
     env.pop("MAXK_VALIDATE", None)  # the bench validates its graph once itself
     root = os.path.dirname(HERE)
-    p = subprocess.run([sys.executable, "-u", os.path.join(root, "bench.py"), "--gpus", str(gpus),
-                        "--graph", graph, "--k", str(k), "--steps", "2", "--warmup", "1",
-                        "--full"],  # --full: the unsharded self-check and the adjoint identity
-                       env=env, cwd=root, capture_output=True, text=True, timeout=280)
+    p = subprocess.Popen([sys.executable, "-u", os.path.join(root, "bench.py"), "--gpus",
+                          str(gpus), "--graph", graph, "--k", str(k), "--steps", "2",
+                          "--warmup", "1",
+                          "--full"],  # --full: the unsharded self-check and the adjoint identity
+                         env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                         text=True)
+    try:
+        stdout, stderr = p.communicate(timeout=280)
+    except BaseException:
+        _kill_tree(p.pid)
+        p.wait()
+        raise
     if p.returncode != 0:
         # a failing rank's own traceback sits above torch.distributed.run's summary
-        lines = p.stderr.splitlines()
+        lines = stderr.splitlines()
         hits = [i for i, ln in enumerate(lines) if "Traceback" in ln or "Error" in ln]
         first = "\n".join(lines[max(0, hits[0] - 2):hits[0] + 40]) if hits else ""
-        raise AssertionError(f"rc {p.returncode}\n{first}\n...\n{p.stderr[-1500:]}")
-    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    assert len(lines) == 1, p.stdout[-2000:]
+        raise AssertionError(f"rc {p.returncode}\n{first}\n...\n{stderr[-1500:]}")
+    lines = [ln for ln in stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, stdout[-2000:]
     d = json.loads(lines[0])
     e = d["extra"]
     V = {"products": 2449029, "reddit": 232965}[graph]
