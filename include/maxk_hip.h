@@ -954,6 +954,54 @@ int maxk_spgemm_max_backward(const int32_t *row_ptr, const int32_t *col_idx,
                              int32_t dim_origin, int32_t dim_k, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * A linear layer on CBSR features (cbsr_linear.hip).  cbsr_val f32 / cbsr_idx u8 [num_rows,
+ * dim_k], 1 <= dim_k <= dim_origin <= 256; weight f32 [out_feats, dim_origin] row-major
+ * (nn.Linear.weight), any out_feats >= 1.
+ *   forward   y[v, o]      = (accumulate ? y[v, o] : 0) + (bias ? bias[o] : 0)
+ *                            + sum_j cbsr_val[v, j] * weight[o, cbsr_idx[v, j]]   in slot order
+ *   values    grad_val[v, j] = sum_o grad_out[v, o] * weight[o, cbsr_idx[v, j]]
+ *   weight    grad_weight[o, d] = sum_v sum_{j : cbsr_idx[v, j] = d} grad_out[v, o] * cbsr_val[v, j]
+ * A selector >= dim_origin contributes nothing (its grad_val slot is exactly 0); a repeated
+ * selector's slots each count; there are no implicit zero terms, so a NaN or Inf in column d of
+ * weight reaches only the rows that select d, and a column of grad_weight no row selects is
+ * exactly 0.  Every element of y, grad_val and grad_weight is written; num_rows == 0 launches
+ * nothing for the first two and writes zeros to grad_weight.
+ * fp32 throughout, no atomics in global memory, every sum in a fixed order: bitwise repeatable
+ * on one device for one chunk_rows (the weight gradient's grouping of rows into partial tiles
+ * follows the device's CU count and chunk_rows).
+ * chunk_rows: rows per work item, 0 = automatic.  bias may be NULL.  The forward takes no
+ * workspace; the value gradient's is [tiles, num_rows, dim_k] when out_feats spans several tiles;
+ * the weight gradient's holds one [128, dim_origin] partial per workgroup, summed in workgroup
+ * order by a second kernel.
+ * maxk_cbsr_linear_route: 1 where the measurements (profiles/r24/cbsr_linear/) say the forward
+ * and the value gradient beat the dense products they replace: dim_k <= dim_origin / 16.  It says
+ * nothing for the weight gradient, which loses to the dense product at every measured point but
+ * one (233 K rows, dim_k = 8); a step that runs all three kernels was a net win at 233 K rows and
+ * a net loss at 2.45 M rows where the route answers 1.
+ * ------------------------------------------------------------------------- */
+int maxk_cbsr_linear_forward(const float *cbsr_val, const uint8_t *cbsr_idx, const float *weight,
+                             const float *bias, float *y, int64_t num_rows, int32_t dim_origin,
+                             int32_t dim_k, int64_t out_feats, int32_t accumulate,
+                             int32_t chunk_rows, void *stream);
+size_t maxk_cbsr_linear_backward_values_workspace_size(int64_t num_rows, int32_t dim_origin,
+                                                       int32_t dim_k, int64_t out_feats,
+                                                       int32_t chunk_rows);
+int maxk_cbsr_linear_backward_values(const float *grad_out, const uint8_t *cbsr_idx,
+                                     const float *weight, float *grad_val, int64_t num_rows,
+                                     int32_t dim_origin, int32_t dim_k, int64_t out_feats,
+                                     int32_t chunk_rows, void *workspace, size_t workspace_bytes,
+                                     void *stream);
+size_t maxk_cbsr_linear_backward_weight_workspace_size(int64_t num_rows, int32_t dim_origin,
+                                                       int32_t dim_k, int64_t out_feats,
+                                                       int32_t chunk_rows);
+int maxk_cbsr_linear_backward_weight(const float *grad_out, const float *cbsr_val,
+                                     const uint8_t *cbsr_idx, float *grad_weight,
+                                     int64_t num_rows, int32_t dim_origin, int32_t dim_k,
+                                     int64_t out_feats, int32_t chunk_rows, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+int maxk_cbsr_linear_route(int32_t dim_origin, int32_t dim_k, int64_t out_feats);
+
 /* Transpose plan of a CSR graph (once per graph): col_ptr[num_cols+1] of the
  * CSC and csc_eid[num_e] = the CSR edge id held by CSC slot t (stable in CSR order).
  * Replaces the CSC side files of generate_meta_csc.py:14-93 /

@@ -55,6 +55,8 @@ __all__ = [
     "dot_attention_heads", "dot_edge_alpha_heads", "dot_attention_heads_backward",
     "dot_attention_backward_route",
     "spgemm_max_forward", "spgemm_max_backward",
+    "cbsr_linear_forward", "cbsr_linear_backward_values", "cbsr_linear_backward_weight",
+    "cbsr_linear_route",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -930,6 +932,100 @@ def spgemm_max_backward(indptr: torch.Tensor, indices: torch.Tensor, idx: torch.
                (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(idx), _ptr(arg),
                 _ptr(grad_out), _ptr(grad_vals), *shape))
     return grad_vals
+
+
+def _same_device(ref, *named):
+    """The launch runs on ref's device with raw pointers: every other operand lives there."""
+    for t, n in named:
+        if t is not None and t.device != ref.device:
+            raise RuntimeError(f"{n} must be on {ref.device}, got {t.device}")
+
+
+def _linear_operands(idx, weight, rows_of, name):
+    """(V, k, D, O) of a CBSR linear call; rows_of [V, *] is the call's other row operand."""
+    _need(idx, "sparse_selector", torch.uint8)
+    _need(weight, "weight", torch.float32)
+    _need(rows_of, name, torch.float32)
+    if idx.dim() != 2 or weight.dim() != 2 or rows_of.dim() != 2 or rows_of.shape[0] != idx.shape[0]:
+        raise RuntimeError(f"sparse_selector must be [V, k], weight [O, D], {name} [V, *]")
+    _same_device(rows_of, (idx, "sparse_selector"), (weight, "weight"))
+    return idx.shape[0], idx.shape[1], weight.shape[1], weight.shape[0]
+
+
+def cbsr_linear_forward(vals: torch.Tensor, idx: torch.Tensor, weight: torch.Tensor,
+                        bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                        chunk_rows: int = 0) -> torch.Tensor:
+    """y [V, O] = scatter(vals, idx) @ weight^T (+ bias) without the zeros: k products per
+    output (maxk_cbsr_linear_forward).  out=: y is added onto it in place (SAGE's neighbour term
+    already there) and returned.  weight [O, D] is nn.Linear.weight; a selector >= D contributes
+    nothing."""
+    V, k, D, O = _linear_operands(idx, weight, vals, "vals")
+    if vals.shape != idx.shape:
+        raise RuntimeError("vals and sparse_selector must both be [V, k]")
+    dev = vals.device
+    if bias is not None:
+        _need(bias, "bias", torch.float32)
+        if bias.shape != (O,):
+            raise RuntimeError("bias must be [O]")
+    if out is not None:
+        _need(out, "out", torch.float32)
+        if out.shape != (V, O):
+            raise RuntimeError("out must be [V, O]")
+    _same_device(vals, (bias, "bias"), (out, "out"))
+    y = out if out is not None else torch.empty(V, O, dtype=torch.float32, device=dev)
+    _launch(dev, "maxk_cbsr_linear_forward", _ptr(vals), _ptr(idx), _ptr(weight), _ptr(bias),
+            _ptr(y), V, D, k, O, int(out is not None), int(chunk_rows), _stream(dev))
+    return y
+
+
+def cbsr_linear_backward_values(grad_out: torch.Tensor, idx: torch.Tensor, weight: torch.Tensor,
+                                chunk_rows: int = 0) -> torch.Tensor:
+    """grad_vals [V, k] of cbsr_linear_forward: grad_out @ weight gathered at each row's selected
+    columns, without the [V, D] product (maxk_cbsr_linear_backward_values).  A slot whose
+    selector is >= D gets exactly 0."""
+    V, k, D, O = _linear_operands(idx, weight, grad_out, "grad_out")
+    if grad_out.shape[1] != O:
+        raise RuntimeError("grad_out must be [V, O]")
+    dev = grad_out.device
+    gval = torch.empty(V, k, dtype=torch.float32, device=dev)
+    shape = (V, D, k, O, int(chunk_rows))
+    _launch_ws(dev, "maxk_cbsr_linear_backward_values",
+               "maxk_cbsr_linear_backward_values_workspace_size", shape,
+               (_ptr(grad_out), _ptr(idx), _ptr(weight), _ptr(gval), *shape))
+    return gval
+
+
+def cbsr_linear_backward_weight(grad_out: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor,
+                                dim: int, chunk_rows: int = 0) -> torch.Tensor:
+    """grad_weight [O, dim] of cbsr_linear_forward: grad_out^T @ scatter(vals, idx) from the k
+    kept values of each row (maxk_cbsr_linear_backward_weight): per-workgroup partial tiles,
+    summed in a fixed order; a column no row selects is exactly 0."""
+    _need(idx, "sparse_selector", torch.uint8)
+    _need(vals, "vals", torch.float32)
+    _need(grad_out, "grad_out", torch.float32)
+    if idx.dim() != 2 or vals.shape != idx.shape or grad_out.dim() != 2 or \
+            grad_out.shape[0] != idx.shape[0]:
+        raise RuntimeError("vals and sparse_selector must be [V, k], grad_out [V, O]")
+    _same_device(grad_out, (vals, "vals"), (idx, "sparse_selector"))
+    V, k = idx.shape
+    D, O = int(dim), grad_out.shape[1]
+    dev = grad_out.device
+    gw = torch.empty(O, D, dtype=torch.float32, device=dev)
+    shape = (V, D, k, O, int(chunk_rows))
+    _launch_ws(dev, "maxk_cbsr_linear_backward_weight",
+               "maxk_cbsr_linear_backward_weight_workspace_size", shape,
+               (_ptr(grad_out), _ptr(vals), _ptr(idx), _ptr(gw), *shape))
+    return gw
+
+
+def cbsr_linear_route(D: int, k: int, O: int) -> bool:
+    """Whether cbsr_linear_forward and cbsr_linear_backward_values beat the dense products they
+    replace (x_sparse @ W^T; g @ W with the top-k gather) at (D, k, O): k <= D / 16, the rule the
+    measurements under profiles/r24/cbsr_linear/ support.  It is NOT where the layer option pays:
+    cbsr_linear_backward_weight loses to _wgrad at every measured point but one, so a training
+    step on all three kernels (maxk_cbsr_linear, sparse_self=True) was a net win at 233 K rows
+    and a net loss at 2.45 M rows where this answers True."""
+    return bool(_L.maxk_cbsr_linear_route(int(D), int(k), int(O)))
 
 
 def dot_attention_backward_route(num_heads: int, num_rows: int, num_e: int, k: int) -> str:

@@ -136,6 +136,15 @@ SIGNATURES = {
     "maxk_spgemm_max_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32]),
     "maxk_spgemm_max_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                                 _i32, _i32, _p, _sz, _p]),
+    "maxk_cbsr_linear_forward": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _i32,
+                                                _i32, _p]),
+    "maxk_cbsr_linear_backward_values_workspace_size": (_sz, [_i64, _i32, _i32, _i64, _i32]),
+    "maxk_cbsr_linear_backward_values": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i64,
+                                                        _i32, _p, _sz, _p]),
+    "maxk_cbsr_linear_backward_weight_workspace_size": (_sz, [_i64, _i32, _i32, _i64, _i32]),
+    "maxk_cbsr_linear_backward_weight": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i64,
+                                                        _i32, _p, _sz, _p]),
+    "maxk_cbsr_linear_route": (ctypes.c_int, [_i32, _i32, _i64]),
     "maxk_sspmm_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
     "maxk_sspmm_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                            _i32, _i32, _i32, _p, _sz, _p]),

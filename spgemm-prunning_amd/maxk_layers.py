@@ -259,6 +259,41 @@ def linear(x: torch.Tensor, layer: nn.Linear, x2: Optional[torch.Tensor] = None,
     return out
 
 
+class _CBSRLinear(Function):
+    """out (+)= scatter(vals, idx) W^T (+ b) from the k kept values of each row: the three
+    mk.cbsr_linear_* kernels instead of three [V, D] x [D, O] products.  The value gradient is
+    [V, k] and reaches the layer input through MaxK.backward."""
+
+    @staticmethod
+    def forward(ctx, vals, idx, w, b, out):
+        vals, w = vals.float().contiguous(), w.contiguous()
+        if out is not None:
+            ctx.mark_dirty(out)
+        y = mk.cbsr_linear_forward(vals, idx, w, b, out=out)
+        ctx.save_for_backward(vals, idx, w)
+        ctx.has_b, ctx.has_out = b is not None, out is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        vals, idx, w = ctx.saved_tensors
+        g = g.contiguous()
+        n = ctx.needs_input_grad
+        gv = mk.cbsr_linear_backward_values(g, idx, w) if n[0] else None
+        gw = mk.cbsr_linear_backward_weight(g, vals, idx, w.shape[1]) if n[2] else None
+        gb = _bgrad(g) if ctx.has_b and n[3] else None
+        return gv, None, gw, gb, g if ctx.has_out and n[4] else None
+
+
+def maxk_cbsr_linear(vals: torch.Tensor, idx: torch.Tensor, weight: torch.Tensor,
+                     bias: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.linear(scatter(vals, idx), weight, bias) on the CBSR (vals f32 [V, k], idx u8 [V, k],
+    weight [O, D]), added in place onto `out` [V, O] when given.  Gradients reach vals, weight,
+    bias and out."""
+    return _CBSRLinear.apply(vals, idx, weight, bias, out)
+
+
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """F.cross_entropy(logits, target) (mean over rows) as log_softmax + gather + mean:
     PyTorch's nll_loss reduction kernel takes 5 ms forward + 4 ms backward on 2.45M rows,
@@ -276,12 +311,20 @@ class MaxKSAGEConv(nn.Module):
     run on the CBSR (CSRGraph.aggregate_max; a neighbour that does not keep a column competes
     with 0 there, as its masked dense feature would).  pool_k: the k of that MaxK (default: the
     k of the topk_values passed in).  fc_pool is Xavier-initialised with the ReLU gain, as DGL
-    does.  "mean" keeps its parameters, their initialisation and its state_dict keys."""
+    does.  "mean" keeps its parameters, their initialisation and its state_dict keys.
+    sparse_self=True: the fc_self term comes from maxk_cbsr_linear on the (post-dropout)
+    topk_values, accumulated onto fc_neigh(agg) -- k products per output instead of in_feats, in
+    the forward and in both gradients; same parameters and state_dict keys.  Measured
+    (profiles/r24/cbsr_linear/): the forward and the value gradient win for k <= in_feats / 16
+    (mk.cbsr_linear_route), the weight gradient does not, and the step was faster at 233 K
+    vertices with k <= 16 only.  Refused with reference_compat, where the aggregation and the self
+    term see different values.  MAXK_CBSR_LINEAR=0|1 overrides the argument of every layer but
+    the reference_compat ones, which stay dense."""
 
     def __init__(self, in_feats: int, out_feats: int, bias: bool = True, feat_drop: float = 0.,
                  activation=None, norm: Optional[nn.Module] = None,
                  reference_compat: bool = False, aggregator_type: str = "mean",
-                 pool_k: Optional[int] = None):
+                 pool_k: Optional[int] = None, sparse_self: bool = False):
         super().__init__()
         valid_aggre_types = {"mean", "pool"}
         if aggregator_type not in valid_aggre_types:
@@ -289,7 +332,11 @@ class MaxKSAGEConv(nn.Module):
                              f"But got {aggregator_type!r} instead.")
         self.aggregator_type, self.pool_k = aggregator_type, pool_k
         self.in_feats, self.out_feats = in_feats, out_feats
-        self.reference_compat = reference_compat
+        self.reference_compat, self.sparse_self = reference_compat, bool(sparse_self)
+        if self.sparse_self and reference_compat:
+            raise ValueError("sparse_self is not combined with reference_compat: there the "
+                             "aggregation sees the undropped topk_values and fc_self the "
+                             "dropped features")
         self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
         self.fc_self = nn.Linear(in_feats, out_feats, bias=bias)
         self.feat_drop = nn.Dropout(feat_drop)
@@ -300,6 +347,13 @@ class MaxKSAGEConv(nn.Module):
         if aggregator_type == "pool":  # after the others: "mean" draws the same numbers as ever
             self.fc_pool = nn.Linear(in_feats, in_feats)
             nn.init.xavier_uniform_(self.fc_pool.weight, gain=gain)
+
+    def sparse_self_on(self) -> bool:
+        """Whether fc_self runs on the CBSR: MAXK_CBSR_LINEAR when it is 0 or 1, else the
+        `sparse_self` argument; a reference_compat layer never does."""
+        forced = os.environ.get("MAXK_CBSR_LINEAR", "")
+        on = forced == "1" if forced in ("0", "1") else self.sparse_self
+        return on and not self.reference_compat
 
     def forward(self, graph: CSRGraph, x_sparse, topk_values, topk_indices):
         deg = _clamped(graph, "in_degrees")
@@ -313,8 +367,11 @@ class MaxKSAGEConv(nn.Module):
             agg = graph.aggregate_max(pv, pi, self.in_feats)
         else:
             agg = graph.aggregate(topk_values, topk_indices, self.in_feats, row_div=deg)
-        # fc_self(x) + fc_neigh(agg) as one accumulated pair of GEMMs
-        rst = linear(h_self, self.fc_self, agg, self.fc_neigh)
+        if self.sparse_self_on():  # fc_neigh(agg), then the self term added by the CBSR kernel
+            rst = maxk_cbsr_linear(topk_values, topk_indices, self.fc_self.weight,
+                                   self.fc_self.bias, out=linear(agg, self.fc_neigh))
+        else:  # fc_self(x) + fc_neigh(agg) as one accumulated pair of GEMMs
+            rst = linear(h_self, self.fc_self, agg, self.fc_neigh)
         if self.activation is not None:
             rst = self.activation(rst)
         if self.norm is not None:
@@ -787,7 +844,8 @@ class MaxKSAGE(nn.Module):
 
     def __init__(self, in_size: int, hid_size: int, num_hid_layers: int, out_size: int,
                  maxk: int = 32, feat_drop: float = 0.5, norm: bool = False,
-                 nonlinear: str = "maxk", graph_name: str = "", reference_compat: bool = False):
+                 nonlinear: str = "maxk", graph_name: str = "", reference_compat: bool = False,
+                 sparse_self: bool = False):
         super().__init__()
         if nonlinear != "maxk":
             raise ValueError(f"Only 'maxk' supported, got {nonlinear}")
@@ -797,7 +855,7 @@ class MaxKSAGE(nn.Module):
         self.layers = nn.ModuleList([
             MaxKSAGEConv(hid_size, hid_size, feat_drop=feat_drop,
                          norm=nn.LayerNorm(hid_size) if norm else None,
-                         reference_compat=reference_compat)
+                         reference_compat=reference_compat, sparse_self=sparse_self)
             for _ in range(num_hid_layers)])
         self.lin_out = nn.Linear(hid_size, out_size)
         nn.init.xavier_uniform_(self.lin_in.weight)

@@ -129,6 +129,9 @@ def main(argv=None):
     ap.add_argument("--reorder", action="store_true",
                     help="relabel the graph by maxk_graph.locality_order first (untimed, once "
                          "per graph; features and labels are synthetic, so none to permute)")
+    ap.add_argument("--sparse-self", action="store_true",
+                    help="fc_self on the CBSR (MaxKSAGEConv(sparse_self=True): the "
+                         "mk.cbsr_linear_* kernels); the library model keeps the dense products")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("maxk_train_bench needs an MI355X (HIP device)")
@@ -159,9 +162,12 @@ def main(argv=None):
     model = maxk_layers.MaxKSAGE(f_in, args.hidden, args.layers, n_cls, maxk=args.k,
                                  feat_drop=0.0).to(dev)
     ref = copy.deepcopy(model)
+    for layer in model.layers:
+        layer.sparse_self = args.sparse_self
     ms, loss0, loss_n = time_epochs(model, g, x, y, args.epochs, args.warmup)
     out = {"graph": args.graph, "source": source, "V": V, "E": indices.numel(),
            "hidden": args.hidden, "k": args.k, "layers": args.layers, "epochs": args.epochs,
+           "sparse_self": bool(model.layers[0].sparse_self_on()),
            "maxk_epoch_ms": round(ms, 3), "first_loss": loss0, "last_loss": loss_n}
     if args.reorder:
         out["reorder_s"] = t_reorder
