@@ -1002,6 +1002,32 @@ int maxk_cbsr_linear_backward_weight(const float *grad_out, const float *cbsr_va
                                      size_t workspace_bytes, void *stream);
 int maxk_cbsr_linear_route(int32_t dim_origin, int32_t dim_k, int64_t out_feats);
 
+/* ---------------------------------------------------------------------------
+ * Fused linear + MaxK (linear_maxk.hip): the CBSR of topk_k(x @ weight^T (+ bias)) without the
+ * dense hidden matrix.  x f32 [num_rows, in_dim] with row stride ld_x >= in_dim; weight f32
+ * [dim, in_dim] row-major (nn.Linear.weight); bias f32 [dim] or NULL; cbsr_val f32 / cbsr_idx
+ * u8 [num_rows, k].  1 <= k <= dim <= 256, any in_dim >= 1, any num_rows >= 0 (0 launches
+ * nothing).  An fp32 MFMA GEMM (fp32 operands, fp32 accumulation, no reduced-precision path)
+ * whose epilogue runs maxk_topk_cbsr's own row selection on the sums: a row's k winners come
+ * out value descending, column ascending on ties, NaN largest, and cbsr_val holds the sums
+ * that were ranked.  The bias is added once, after the sum over in_dim.  Each row's sum runs
+ * in an order fixed by in_dim alone: bitwise repeatable and invariant under a permutation of
+ * the rows of x.  No global atomics, no split-K, no workspace.  A row whose search ends with
+ * other than k winners is counted for maxk_topk_error_rows.
+ * Replaces: the Linear (model_integrated_v3.py) + MaxK's torch.topk
+ *           (maxk_spgemm_function.py:51-57) pair at the head of every MaxK layer, here
+ *           torch.addmm followed by maxk_topk_cbsr.
+ * maxk_linear_maxk_route: 1 where the measurements (profiles/r25/linear_maxk/) say the fused
+ * forward beats that pair in time: at none of the 24 measured points (the pair was faster at 23
+ * and level at one), so it answers 0 for every shape.  The fused call's gain is memory: its
+ * peak is lower by the 4 * num_rows * dim bytes of the product.
+ * ------------------------------------------------------------------------- */
+int maxk_linear_maxk_forward(const float *x, int64_t ld_x, const float *weight,
+                             const float *bias, float *cbsr_val, uint8_t *cbsr_idx,
+                             int64_t num_rows, int32_t in_dim, int32_t dim, int32_t k,
+                             void *stream);
+int maxk_linear_maxk_route(int64_t num_rows, int32_t in_dim, int32_t dim, int32_t k);
+
 /* Transpose plan of a CSR graph (once per graph): col_ptr[num_cols+1] of the
  * CSC and csc_eid[num_e] = the CSR edge id held by CSC slot t (stable in CSR order).
  * Replaces the CSC side files of generate_meta_csc.py:14-93 /

@@ -704,6 +704,17 @@ __global__ __launch_bounds__(kBlock) void topk_u8_reference_kernel(const uint8_t
 }
 
 }  // namespace
+
+// The device address of this device's bad-row counter, for linear_maxk.hip, whose epilogue runs
+// the same selections (topk_select.h) and counts into it; NULL if the runtime cannot name it.
+uint32_t *topk_bad_rows_counter() {
+    void *p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_topk_bad_rows)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return reinterpret_cast<uint32_t *>(p);
+}
 }  // namespace maxk
 
 using namespace maxk;

@@ -56,7 +56,7 @@ __all__ = [
     "dot_attention_backward_route",
     "spgemm_max_forward", "spgemm_max_backward",
     "cbsr_linear_forward", "cbsr_linear_backward_values", "cbsr_linear_backward_weight",
-    "cbsr_linear_route",
+    "cbsr_linear_route", "linear_maxk_forward", "linear_maxk_route",
     "version", "device_count",
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
@@ -1026,6 +1026,50 @@ def cbsr_linear_route(D: int, k: int, O: int) -> bool:
     step on all three kernels (maxk_cbsr_linear, sparse_self=True) was a net win at 233 K rows
     and a net loss at 2.45 M rows where this answers True."""
     return bool(_L.maxk_cbsr_linear_route(int(D), int(k), int(O)))
+
+
+def linear_maxk_forward(x: torch.Tensor, weight: torch.Tensor,
+                        bias: Optional[torch.Tensor] = None, *, k: int):
+    """(values [V, k], uint8 indices [V, k]) = topk_cbsr(x @ weight^T (+ bias), k) in one kernel
+    (maxk_linear_maxk_forward): an fp32 MFMA GEMM whose epilogue runs the encode's row selection
+    on the accumulators, so the dense [V, D] product is never allocated or written.  weight
+    [D, I] is nn.Linear.weight; x [V, I] may be a column slice of a wider tensor (unit column
+    stride).  Refused: D > 256, k outside [1, D], anything but float32."""
+    for t, n in ((x, "x"), (weight, "weight")) + (((bias, "bias"),) if bias is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{n} must be a float32 CUDA tensor")
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or x.shape[1] < 1:
+        raise RuntimeError("x must be [V, I] and weight [D, I], I >= 1")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    _need(weight, "weight", torch.float32)
+    (V, I), D, k = x.shape, weight.shape[0], int(k)
+    if not 1 <= D <= 256:
+        raise RuntimeError(f"weight has {D} rows: the fused linear + MaxK serves D <= 256")
+    if not 1 <= k <= D:
+        raise RuntimeError(f"k = {k} must be in [1, D = {D}]")
+    if bias is not None:
+        _need(bias, "bias", torch.float32)
+        if bias.shape != (D,):
+            raise RuntimeError("bias must be [D]")
+    _same_device(x, (weight, "weight"), (bias, "bias"))
+    dev = x.device
+    val = torch.empty(V, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(V, k, dtype=torch.uint8, device=dev)
+    check = V > 0 and _checks_topk_rows(dev)
+    _launch(dev, "maxk_linear_maxk_forward", _ptr(x), x.stride(0) if V > 1 else max(I, x.stride(0)),
+            _ptr(weight), _ptr(bias), _ptr(val), _ptr(idx), V, I, D, k, _stream(dev))
+    if check:
+        _check_topk_rows(dev, "maxk_linear_maxk_forward")
+    return val, idx
+
+
+def linear_maxk_route(V: int, I: int, D: int, k: int) -> bool:
+    """Whether linear_maxk_forward beats torch.addmm followed by topk_cbsr in time at
+    (V, I, D, k) (maxk_linear_maxk_route): False for every shape -- under
+    profiles/r25/linear_maxk/ the pair was faster at 23 of the 24 measured points and level at
+    one.  What the fused call saves is the [V, D] product's memory."""
+    return bool(_L.maxk_linear_maxk_route(int(V), int(I), int(D), int(k)))
 
 
 def dot_attention_backward_route(num_heads: int, num_rows: int, num_e: int, k: int) -> str:

@@ -145,6 +145,9 @@ SIGNATURES = {
     "maxk_cbsr_linear_backward_weight": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i64,
                                                         _i32, _p, _sz, _p]),
     "maxk_cbsr_linear_route": (ctypes.c_int, [_i32, _i32, _i64]),
+    "maxk_linear_maxk_forward": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32,
+                                                _p]),
+    "maxk_linear_maxk_route": (ctypes.c_int, [_i64, _i32, _i32, _i32]),
     "maxk_sspmm_backward_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
     "maxk_sspmm_backward": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                            _i32, _i32, _i32, _p, _sz, _p]),

@@ -294,6 +294,38 @@ def maxk_cbsr_linear(vals: torch.Tensor, idx: torch.Tensor, weight: torch.Tensor
     return _CBSRLinear.apply(vals, idx, weight, bias, out)
 
 
+class _LinearMaxK(Function):
+    """(vals, idx) = MaxK's CBSR of x W^T (+ b) from one kernel (mk.linear_maxk_forward): the
+    dense [V, D] product is neither written nor saved.  The backward rebuilds the dense gradient
+    from g_vals as a transient (mk.topk_backward) and then runs _Linear's three products."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, k):
+        x, w = x.float(), w.contiguous()
+        vals, idx = mk.linear_maxk_forward(x, w, b, k=int(k))
+        ctx.save_for_backward(x, w, idx)
+        ctx.has_b = b is not None
+        ctx.mark_non_differentiable(idx)
+        return vals, idx
+
+    @staticmethod
+    def backward(ctx, g_vals, g_idx):
+        x, w, idx = ctx.saved_tensors
+        n = ctx.needs_input_grad
+        g = mk.topk_backward(g_vals.float().contiguous(), None, idx, w.shape[0])
+        gx = g @ w if n[0] else None
+        gw = _wgrad(g, x) if n[1] else None
+        gb = _bgrad(g) if ctx.has_b and n[2] else None
+        return gx, gw, gb, None
+
+
+def maxk_linear(x: torch.Tensor, layer: nn.Linear, k: int):
+    """(topk_values [V, k], topk_indices u8 [V, k]) of maxk(layer(x), k) without the dense
+    layer(x): the fused linear + MaxK kernel.  layer.out_features <= 256.  Gradients reach x,
+    layer.weight and layer.bias."""
+    return _LinearMaxK.apply(x, layer.weight, layer.bias, k)
+
+
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """F.cross_entropy(logits, target) (mean over rows) as log_softmax + gather + mean:
     PyTorch's nll_loss reduction kernel takes 5 ms forward + 4 ms backward on 2.45M rows,
@@ -880,6 +912,7 @@ class _MaxKStack(nn.Module):
             raise ValueError(f"Only 'maxk' supported, got {nonlinear}")
         self.k, self.num_layers, self.graph_name = maxk, num_hid_layers, graph_name
         self.reference_compat = reference_compat
+        self.fused_linear_maxk = False  # MaxKGCN(fused_linear_maxk=True)
         self.dropoutlayers = nn.ModuleList([nn.Dropout(feat_drop) for _ in range(num_hid_layers)])
         self.convs = nn.ModuleList([make_conv() for _ in range(num_hid_layers)])
         self.normlayers = nn.ModuleList([nn.LayerNorm(hid_size) for _ in range(num_hid_layers)]
@@ -893,9 +926,25 @@ class _MaxKStack(nn.Module):
         nn.init.xavier_uniform_(self.lin_in.weight)
         nn.init.xavier_uniform_(self.lin_out.weight)
 
+    def fused_linear_maxk_on(self) -> bool:
+        """Whether a layer's Linear and MaxK run as one kernel: MAXK_LINEAR_MAXK when it is 0 or
+        1, else the `fused_linear_maxk` argument; only MaxKGCN's conv works on the CBSR alone,
+        and a reference_compat model never does."""
+        forced = os.environ.get("MAXK_LINEAR_MAXK", "")
+        on = forced == "1" if forced in ("0", "1") else self.fused_linear_maxk
+        return on and isinstance(self, MaxKGCN) and not self.reference_compat
+
     def forward(self, graph: CSRGraph, x):
         x = linear(x, self.lin_in).relu()
+        fused = self.fused_linear_maxk_on()
         for i in range(self.num_layers):
+            if fused:  # no [V, D] hidden activation: the conv reads the CBSR only
+                vals, idx = maxk_linear(x, self.linlayers[i], self.k)
+                vals = nn.functional.dropout(vals, self.dropoutlayers[i].p, self.training)
+                x = self.convs[i](graph, None, vals, idx)
+                if self.normlayers:
+                    x = self.normlayers[i](x)
+                continue
             x = linear(x, self.linlayers[i])
             x_sparse, vals, idx = maxk(x, self.k, self.reference_compat)
             if self.reference_compat:  # :661, :743: the kernel gets the undropped values
@@ -910,15 +959,29 @@ class _MaxKStack(nn.Module):
 
 class MaxKGCN(_MaxKStack):
     """GCN model (model_integrated_v3.py:590-670): MaxKGraphConv(norm="both", no weight, no
-    bias) after a per-layer Linear."""
+    bias) after a per-layer Linear.
+
+    fused_linear_maxk=True: each layer's Linear and MaxK run as one kernel (maxk_linear), so no
+    [V, hid_size] hidden activation is written or kept for the backward; hid_size <= 256.
+    Feature dropout then acts on the k kept values: every kept entry survives with the same
+    probability as before, but the mask is drawn for [V, k] instead of [V, hid_size], from a
+    different place in the RNG stream, so a seeded run differs from the unfused one in training
+    mode.  MAXK_LINEAR_MAXK=0|1 overrides the argument (never for reference_compat models).
+    Opt-in: tools/linear_maxk_bench.py and profiles/r25/linear_maxk/ say where it pays.
+    Parameters and state_dict keys are the same either way."""
 
     def __init__(self, in_size: int, hid_size: int, num_hid_layers: int, out_size: int,
                  maxk: int = 32, feat_drop: float = 0.5, norm: bool = False,
-                 nonlinear: str = "maxk", graph_name: str = "", reference_compat: bool = False):
+                 nonlinear: str = "maxk", graph_name: str = "", reference_compat: bool = False,
+                 fused_linear_maxk: bool = False):
+        if fused_linear_maxk and reference_compat:
+            raise ValueError("fused_linear_maxk is not combined with reference_compat: there "
+                             "the dropout acts on the dense masked row")
         super().__init__(in_size, hid_size, num_hid_layers, out_size, maxk, feat_drop, norm,
                          nonlinear, graph_name, reference_compat,
                          lambda: MaxKGraphConv(hid_size, hid_size, norm="both", weight=False,
                                                bias=False, reference_compat=reference_compat))
+        self.fused_linear_maxk = bool(fused_linear_maxk)
 
     @property
     def gcnlayers(self):

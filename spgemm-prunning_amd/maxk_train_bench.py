@@ -132,7 +132,13 @@ def main(argv=None):
     ap.add_argument("--sparse-self", action="store_true",
                     help="fc_self on the CBSR (MaxKSAGEConv(sparse_self=True): the "
                          "mk.cbsr_linear_* kernels); the library model keeps the dense products")
+    ap.add_argument("--model", choices=("sage", "gcn"), default="sage")
+    ap.add_argument("--fused-linear-maxk", action="store_true",
+                    help="GCN: each layer's Linear and MaxK as one kernel "
+                         "(MaxKGCN(fused_linear_maxk=True)); also reports the peak memory")
     args = ap.parse_args(argv)
+    if args.fused_linear_maxk and args.model != "gcn":
+        ap.error("--fused-linear-maxk needs --model gcn")
     if not torch.cuda.is_available():
         raise SystemExit("maxk_train_bench needs an MI355X (HIP device)")
     dev = torch.device("cuda")
@@ -159,16 +165,22 @@ def main(argv=None):
     x = torch.randn(V, f_in, generator=gen, device=dev)
     y = torch.randint(0, n_cls, (V,), generator=gen, device=dev)
     torch.manual_seed(0)
-    model = maxk_layers.MaxKSAGE(f_in, args.hidden, args.layers, n_cls, maxk=args.k,
-                                 feat_drop=0.0).to(dev)
+    net = maxk_layers.MaxKGCN if args.model == "gcn" else maxk_layers.MaxKSAGE
+    model = net(f_in, args.hidden, args.layers, n_cls, maxk=args.k, feat_drop=0.0).to(dev)
     ref = copy.deepcopy(model)
-    for layer in model.layers:
-        layer.sparse_self = args.sparse_self
+    if args.model == "gcn":
+        model.fused_linear_maxk = args.fused_linear_maxk
+        flag = {"model": "gcn", "fused_linear_maxk": bool(model.fused_linear_maxk_on())}
+    else:
+        for layer in model.layers:
+            layer.sparse_self = args.sparse_self
+        flag = {"sparse_self": bool(model.layers[0].sparse_self_on())}
+    torch.cuda.reset_peak_memory_stats()
     ms, loss0, loss_n = time_epochs(model, g, x, y, args.epochs, args.warmup)
     out = {"graph": args.graph, "source": source, "V": V, "E": indices.numel(),
            "hidden": args.hidden, "k": args.k, "layers": args.layers, "epochs": args.epochs,
-           "sparse_self": bool(model.layers[0].sparse_self_on()),
-           "maxk_epoch_ms": round(ms, 3), "first_loss": loss0, "last_loss": loss_n}
+           **flag, "maxk_epoch_ms": round(ms, 3), "first_loss": loss0, "last_loss": loss_n,
+           "peak_mem_bytes": torch.cuda.max_memory_allocated()}
     if args.reorder:
         out["reorder_s"] = t_reorder
     if not args.no_library:
