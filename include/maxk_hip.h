@@ -1400,6 +1400,64 @@ int maxk_topk_backward(const float *grad_val, const float *grad_dense, const uin
                        void *stream);
 
 /* ---------------------------------------------------------------------------
+ * x16: the core path (encode, forward, backward) for features wider than 256 columns, on
+ * 16-bit selectors (x16_topk.hip, x16_fwd.hip, x16_bwd.hip, x16_pack.h).
+ * Every entry takes 1 <= dim_origin <= 1024 and 1 <= dim_k <= min(dim_origin, 256) and refuses
+ * anything else with MAXK_ERR_INVALID and a message naming the range; dim_origin <= 256 is
+ * served too.  Selectors are uint16_t.  The entries above keep their limit of 256.
+ *
+ * maxk_topk_cbsr_x16: maxk_topk_cbsr's contract (exact, NaN ranked largest, winners stored in
+ * (key descending, column ascending) order); with out_dense != NULL also maxk_topk_cbsr_dense's
+ * masked dense row (row stride dim_origin), written in the same pass.  Counts a row whose search
+ * took other than dim_k winners for maxk_topk_error_rows, like the entries above.
+ *
+ * maxk_topk_backward_x16: maxk_topk_backward's adjoint,
+ *   grad_x[r, :] = 0;  grad_x[r, j] = grad_val[r, l] + grad_dense[r, j]  for j = cbsr_idx[r, l],
+ * grad_val and grad_dense each optional (NULL = zero; grad_dense == NULL is the CBSR -> dense
+ * scatter), grad_x may alias grad_dense; a selector >= dim_origin writes nothing; every row is
+ * written whole.
+ *
+ * maxk_spgemm_forward_x16: maxk_spgemm_forward's semantics -- every output row written (rows
+ * without edges get zeros), no zero-init needed, row_div may be NULL, repeated selectors of a
+ * CBSR row accumulate, selectors >= dim_origin are ignored, num_rows != num_cols allowed -- with
+ * no global atomics: bitwise repeatable, and within the numerics bound stated at the top.
+ * workspace: one packed record [k f32 | k u16 | pad] per column, and a slab row of dim_origin
+ * floats and a row index per work item.  The packed table must stay below 4 GiB
+ * (num_cols * record stride, 6 * dim_k bytes rounded up to a power of two up to 128 B and to
+ * 64 B past it); a larger one is refused.
+ *
+ * maxk_sspmm_backward_x16: grad_cbsr[c, l] = sum_{e=(r->c)} val[e] * G[r, sel[c, l]] / row_div[r]
+ * as the two-phase csc form: phase 1 stores one contribution row per edge, phase 2 is
+ * maxk_sspmm_backward_csc's (the rows summed per destination in CSC slot order): bitwise
+ * repeatable, every element of grad_cbsr written, a column without in-edges exactly 0, a
+ * selector >= dim_origin contributes 0.  col_ptr / csc_eid: maxk_transpose_plan's.
+ * workspace: (num_e + 1) * dim_k floats of contribution rows plus phase 2's slabs.
+ * ------------------------------------------------------------------------- */
+int maxk_topk_cbsr_x16(const float *x, int64_t ld_x, float *cbsr_val, uint16_t *cbsr_idx,
+                       float *out_dense, int64_t num_rows, int32_t dim_origin, int32_t dim_k,
+                       void *stream);
+int maxk_topk_backward_x16(const float *grad_val, const float *grad_dense,
+                           const uint16_t *cbsr_idx, float *grad_x, int64_t num_rows,
+                           int32_t dim_origin, int32_t dim_k, void *stream);
+size_t maxk_spgemm_forward_x16_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                              int32_t dim_origin, int32_t dim_k,
+                                              int32_t chunk_edges);
+int maxk_spgemm_forward_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *edge_val,
+                            const float *cbsr_val, const uint16_t *cbsr_idx, const float *row_div,
+                            float *out, int64_t num_rows, int64_t num_cols, int64_t num_e,
+                            int32_t dim_origin, int32_t dim_k, int32_t chunk_edges,
+                            void *workspace, size_t workspace_bytes, void *stream);
+size_t maxk_sspmm_backward_x16_workspace_size(int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                              int32_t dim_origin, int32_t dim_k,
+                                              int32_t chunk_edges);
+int maxk_sspmm_backward_x16(const int32_t *row_ptr, const int32_t *col_idx, const float *edge_val,
+                            const float *grad_out, const uint16_t *cbsr_idx, const float *row_div,
+                            const int32_t *col_ptr, const int32_t *csc_eid, float *grad_cbsr,
+                            int64_t num_rows, int64_t num_cols, int64_t num_e, int32_t dim_origin,
+                            int32_t dim_k, int32_t chunk_edges, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * warp4 schedule (drop-in for kernels/generate_meta.py:30-48 / generate_meta_csc.py:14-93
  * and the .warp4 files read by load_warp4_metadata, cuda_kernel_bindings.cpp:287-317).
  * maxk_warp4_count: synchronous; number of entries W = sum over rows of ceil(deg/warp_max_nz).

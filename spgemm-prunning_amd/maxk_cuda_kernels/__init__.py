@@ -61,9 +61,12 @@ __all__ = [
     "transpose_plan", "bsort_plan", "pull_plan", "edge_selector_mode", "backward_plan", "BWD_MODES",
     "dense_plan", "hybrid_plan", "pull_locality", "edge_selectors_wanted",
     "pull_stream_plan", "pull_stream_buckets", "PullStreamPlan",
+    "topk_cbsr_x16", "topk_cbsr_dense_x16", "topk_backward_x16", "spgemm_forward_x16",
+    "sspmm_backward_x16", "MAX_DIM_X16",
 ]
 
 FULL_DIM = 256  # the reference binding's fixed output width (cuda_kernel_bindings.cpp:70)
+MAX_DIM_X16 = 1024  # kMaxDimX16 (x16_pack.h): the widest row of the 16-bit-selector entries
 
 
 def _lib():
@@ -2252,6 +2255,147 @@ def topk_backward(grad_val: Optional[torch.Tensor], grad_dense: Optional[torch.T
             raise RuntimeError("out must be [V, dim_origin]")
     _launch(dev, "maxk_topk_backward", _ptr(grad_val), _ptr(grad_dense), _ptr(cbsr_idx), _ptr(out),
             V, dim_origin, k, _stream(dev))
+    return out
+
+
+# --------------------------------------------------------------------------- x16
+# The core path for 1 <= D <= MAX_DIM_X16 on 16-bit selectors (x16_topk.hip, x16_fwd.hip,
+# x16_bwd.hip).  Selectors are torch.int16 tensors the kernels read as uint16: a column index is
+# below 1024, so the sign bit is never set (torch.uint16 lacks too many ops).
+def _x16_encode(x, k, want_dense):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+        raise RuntimeError("x must be a float32 CUDA tensor")
+    if x.dim() != 2:
+        raise RuntimeError("Input must be 2D tensor")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    V, D = x.shape
+    k = int(k)
+    dev = x.device
+    val = torch.empty(V, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(V, k, dtype=torch.int16, device=dev)
+    dense = torch.empty(V, D, dtype=torch.float32, device=dev) if want_dense else None
+    check = _checks_topk_rows(dev)
+    _launch(dev, "maxk_topk_cbsr_x16", _ptr(x), x.stride(0), _ptr(val), _ptr(idx), _ptr(dense),
+            V, D, k, _stream(dev))
+    if check:
+        _check_topk_rows(dev, "maxk_topk_cbsr_x16")
+    return dense, val, idx
+
+
+def topk_cbsr_x16(x: torch.Tensor, k: int):
+    """(values, int16 indices) = torch.topk(x, k, dim=1) for rows of up to MAX_DIM_X16 columns,
+    k <= min(D, 256): topk_cbsr's contract (exact, NaN largest, key descending then column
+    ascending) on 16-bit selectors."""
+    return _x16_encode(x, k, False)[1:]
+
+
+def topk_cbsr_dense_x16(x: torch.Tensor, k: int):
+    """topk_cbsr_dense for rows of up to MAX_DIM_X16 columns: (dense masked x, values, int16
+    indices) from one HIP kernel."""
+    return _x16_encode(x, k, True)
+
+
+def topk_backward_x16(grad_val: Optional[torch.Tensor], grad_dense: Optional[torch.Tensor],
+                      cbsr_idx: torch.Tensor, dim_origin: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """topk_backward on int16 selectors, dim_origin <= MAX_DIM_X16: grad_x =
+    scatter(grad_val + grad_dense[sel]), zero elsewhere; with grad_dense None the CBSR -> dense
+    scatter."""
+    _need(cbsr_idx, "cbsr_idx", torch.int16)
+    V, k = cbsr_idx.shape
+    dev = cbsr_idx.device
+    if grad_val is not None:
+        _need(grad_val, "grad_val", torch.float32)
+        if tuple(grad_val.shape) != (V, k):
+            raise RuntimeError("grad_val must be [V, k]")
+    if grad_dense is not None:
+        _need(grad_dense, "grad_dense", torch.float32)
+        if tuple(grad_dense.shape) != (V, dim_origin):
+            raise RuntimeError("grad_dense must be [V, dim_origin]")
+    if out is None:
+        out = torch.empty(V, dim_origin, dtype=torch.float32, device=dev)
+    else:
+        _need(out, "out", torch.float32)
+        if tuple(out.shape) != (V, dim_origin):
+            raise RuntimeError("out must be [V, dim_origin]")
+    _launch(dev, "maxk_topk_backward_x16", _ptr(grad_val), _ptr(grad_dense), _ptr(cbsr_idx),
+            _ptr(out), V, int(dim_origin), k, _stream(dev))
+    return out
+
+
+def _x16_operands(indptr, indices, values, data, name, cbsr_idx, row_div):
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (values, "values", torch.float32), (data, name, torch.float32),
+                     (cbsr_idx, "sparse_selector", torch.int16)):
+        _need(t, n, dt)
+    if cbsr_idx.dim() != 2:
+        raise RuntimeError("sparse_selector must be [V, k]")
+    if values.numel() != indices.numel():
+        raise RuntimeError("values and indices must have the same length")
+    if row_div is not None:
+        _need(row_div, "row_div", torch.float32)
+        if row_div.numel() != indptr.numel() - 1:
+            raise RuntimeError("row_div must have num_rows entries")
+
+
+def spgemm_forward_x16(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
+                       cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor, dim_origin: int,
+                       row_div: Optional[torch.Tensor] = None, chunk: int = 0,
+                       out: Optional[torch.Tensor] = None,
+                       validate: Optional[bool] = None) -> torch.Tensor:
+    """spgemm_forward on int16 selectors, dim_origin <= MAX_DIM_X16, k <= 256
+    (maxk_spgemm_forward_x16): out[num_rows, D] = diag(1/row_div) . A . scatter(cbsr), every row
+    written, bitwise repeatable."""
+    _x16_operands(indptr, indices, values, cbsr_val, "input_data", cbsr_idx, row_div)
+    if cbsr_idx.shape != cbsr_val.shape:
+        raise RuntimeError("input_data and sparse_selector must have the same [V, k] shape")
+    num_cols, k = cbsr_val.shape
+    D = int(dim_origin)
+    num_rows = indptr.numel() - 1
+    _validate_call(validate, indptr, indices, num_cols, cbsr_idx, D)
+    dev = cbsr_val.device
+    if out is None:
+        out = torch.empty(num_rows, D, dtype=torch.float32, device=dev)
+    else:
+        _need(out, "out", torch.float32)
+        if tuple(out.shape) != (num_rows, D):
+            raise RuntimeError("out must be [num_rows, dim_origin]")
+    shape = (num_rows, num_cols, indices.numel(), D, k, chunk)
+    _launch_ws(dev, "maxk_spgemm_forward_x16", "maxk_spgemm_forward_x16_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(cbsr_val), _ptr(cbsr_idx),
+                _ptr(row_div), _ptr(out), *shape))
+    return out
+
+
+def sspmm_backward_x16(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
+                       grad_output: torch.Tensor, cbsr_idx: torch.Tensor,
+                       row_div: Optional[torch.Tensor] = None, chunk: int = 0,
+                       out: Optional[torch.Tensor] = None, validate: Optional[bool] = None,
+                       plan=None) -> torch.Tensor:
+    """sspmm_backward on int16 selectors, grad_output [num_rows, D] with D <= MAX_DIM_X16
+    (maxk_sspmm_backward_x16, the two-phase csc form): grad_cbsr[c, l] = sum over the edges
+    (r -> c) of values[e] * grad_output[r, sel[c, l]] / row_div[r]; bitwise repeatable.  plan:
+    transpose_plan's (col_ptr, csc_eid), taken from its cache when None."""
+    _x16_operands(indptr, indices, values, grad_output, "grad_output", cbsr_idx, row_div)
+    num_rows = indptr.numel() - 1
+    if grad_output.dim() != 2 or grad_output.shape[0] != num_rows:
+        raise RuntimeError("grad_output must be [num_rows, dim_origin]")
+    num_cols, k = cbsr_idx.shape
+    D = grad_output.shape[1]
+    _validate_call(validate, indptr, indices, num_cols, cbsr_idx, D)
+    dev = grad_output.device
+    if out is None:
+        out = torch.empty(num_cols, k, dtype=torch.float32, device=dev)
+    else:
+        _need(out, "out", torch.float32)
+        if tuple(out.shape) != (num_cols, k):
+            raise RuntimeError("out must be [num_cols, k]")
+    col_ptr, csc_eid = plan if plan is not None else transpose_plan(indices, num_cols)
+    shape = (num_rows, num_cols, indices.numel(), D, k, chunk)
+    _launch_ws(dev, "maxk_sspmm_backward_x16", "maxk_sspmm_backward_x16_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(grad_output), _ptr(cbsr_idx),
+                _ptr(row_div), _ptr(col_ptr), _ptr(csc_eid), _ptr(out), *shape))
     return out
 
 

@@ -151,11 +151,13 @@ class MaxK(Function):
     Both directions are single fused HIP passes: the forward writes the
     CBSR and the masked dense row from one top-k kernel (maxk_topk_cbsr_dense); the backward
     gathers the dense gradient at the selected columns, adds the topk_values gradient and
-    writes the whole dense row in one kernel (maxk_topk_backward)."""
+    writes the whole dense row in one kernel (maxk_topk_backward).  Rows wider than 256 columns
+    (up to mk.MAX_DIM_X16) take the 16-bit-selector encode and adjoint: topk_indices is int16."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, k: int, drop_topk_grad: bool = False):
-        dense, vals, idx = mk.topk_cbsr_dense(x.float(), int(k))
+        encode = mk.topk_cbsr_dense_x16 if x.shape[1] > 256 else mk.topk_cbsr_dense
+        dense, vals, idx = encode(x.float(), int(k))
         ctx.save_for_backward(idx)
         ctx.D = x.shape[1]
         ctx.drop = bool(drop_topk_grad)
@@ -171,7 +173,8 @@ class MaxK(Function):
         gd = None if g_dense is None else g_dense.float().contiguous()
         if gv is None and gd is None:
             return None, None, None
-        return mk.topk_backward(gv, gd, idx, ctx.D), None, None
+        adjoint = mk.topk_backward_x16 if idx.dtype == torch.int16 else mk.topk_backward
+        return adjoint(gv, gd, idx, ctx.D), None, None
 
 
 def maxk(x: torch.Tensor, k: int, reference_compat: bool = False):

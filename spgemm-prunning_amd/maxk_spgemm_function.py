@@ -170,13 +170,43 @@ def _save(ctx, base, cbsr_val, fwd_div):
     ctx.save_for_backward(*base)
 
 
+X16_WGRAD_ERROR = ("the edge-weight gradient is not available on the x16 path (dim_origin > 256 "
+                   "or int16 selectors): pass graph_values that do not require grad")
+
+
+def _sel16(topk_indices):
+    """Selectors of the x16 path: int16, whatever integer type the caller holds them in."""
+    sel = topk_indices if topk_indices.dtype == torch.int16 else topk_indices.to(torch.int16)
+    return sel.contiguous()
+
+
+def _forward_x16(ctx, indptr, graph_indices, graph_values, vals, sel, D, row_div, bwd_div):
+    """The forward of both call shapes on 16-bit selectors (maxk_cuda_kernels.spgemm_forward_x16);
+    the backward is sspmm_backward_x16, the two-phase csc form."""
+    if ctx.needs_input_grad[1]:
+        raise RuntimeError(X16_WGRAD_ERROR)
+    ctx.wgrad = False
+    ctx.bwd_mode = ctx.es_mode = None
+    out = maxk_cuda_kernels.spgemm_forward_x16(indptr, graph_indices, _f32(graph_values), vals,
+                                               sel, D, row_div=row_div)
+    _save(ctx, (indptr, graph_indices, graph_values, sel,
+                bwd_div if bwd_div is not None else torch.empty(0), torch.empty(0)), vals, row_div)
+    ctx.has_div = bwd_div is not None
+    ctx.has_es = False
+    ctx.x16 = True
+    return out
+
+
 class MaxKSpGEMMFunction(Function):
-    """Autograd function over the HIP forward SpGEMM / backward SSpMM (both call shapes)."""
+    """Autograd function over the HIP forward SpGEMM / backward SSpMM (both call shapes).
+    Features wider than 256 columns (v1: input_features.shape[1] > 256; v4: dim_origin > 256 or
+    int16 topk_indices) take the 16-bit-selector kernels, up to 1024 columns."""
 
     @staticmethod
     def forward(ctx, graph_indices, graph_values, a3, a4, *rest):
         _require_kernels()
         graph_indices = _i32(graph_indices)
+        ctx.x16 = False
         if isinstance(a4, torch.Tensor):
             out = MaxKSpGEMMFunction._forward_v4(ctx, graph_indices, graph_values, a3, a4, *rest)
         else:
@@ -193,12 +223,15 @@ class MaxKSpGEMMFunction(Function):
         x = _f32_act(input_features)
         V, D = x.shape
         k = int(k_value)
+        x16 = D > FULL_DIM
         if k < D:
-            sparse_data, sparse_selector = maxk_cuda_kernels.topk_cbsr(x, k)
+            sparse_data, sparse_selector = (maxk_cuda_kernels.topk_cbsr_x16 if x16
+                                            else maxk_cuda_kernels.topk_cbsr)(x, k)
         else:  # k >= D: all features, identity selector (maxk_spgemm_function.py:58-63)
             k = D
             sparse_data = x
-            sparse_selector = torch.arange(D, device=x.device, dtype=torch.uint8) \
+            sparse_selector = torch.arange(D, device=x.device,
+                                           dtype=torch.int16 if x16 else torch.uint8) \
                 .unsqueeze(0).expand(V, -1).contiguous()
         indptr = _indptr_for(graph_indptr, warp4_metadata, num_warps, V)
         row_div = _f32(in_degrees)
@@ -208,6 +241,11 @@ class MaxKSpGEMMFunction(Function):
         # the backward's divisor of G's rows: the forward's own (the exact adjoint), or the
         # reference's rule, G / out_degrees when given and G undivided otherwise (:154-159)
         bwd_div = _f32(out_degrees) if backward_divisor == "reference" else row_div
+        ctx.shape_v1 = (V, D)
+        ctx.mode = "v1"
+        if x16:
+            return _forward_x16(ctx, indptr, graph_indices, graph_values, sparse_data,
+                                sparse_selector, D, row_div, bwd_div)
         es, ctx.es_mode = _edge_sel_for(indptr, graph_indices, k, V, D,
                                         _weight_grad_mode(ctx, graph_indices, k, V))
         out = maxk_cuda_kernels.spgemm_forward(indptr, graph_indices, _f32(graph_values),
@@ -228,12 +266,16 @@ class MaxKSpGEMMFunction(Function):
                     warp4_metadata=None, num_warps=0, graph_indptr=None, degrees=None,
                     dim_origin=None):
         vals = _f32_act(topk_values)
-        sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
-        sel = sel.contiguous()
         V, k = vals.shape
         D = int(dim_origin) if dim_origin is not None else FULL_DIM
         indptr = _indptr_for(graph_indptr, warp4_metadata, num_warps, V)
         row_div = _f32(degrees)
+        ctx.mode = "v4"
+        if topk_indices.dtype == torch.int16 or D > FULL_DIM:
+            return _forward_x16(ctx, indptr, graph_indices, graph_values, vals,
+                                _sel16(topk_indices), D, row_div, row_div)
+        sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
+        sel = sel.contiguous()
         es, ctx.es_mode = _edge_sel_for(indptr, graph_indices, k, V, D,
                                         _weight_grad_mode(ctx, graph_indices, k, V))
         out = maxk_cuda_kernels.spgemm_forward(indptr, graph_indices, _f32(graph_values), vals,
@@ -256,10 +298,14 @@ class MaxKSpGEMMFunction(Function):
         # with the forward's edge-selector stream the backward is the two-phase form (csc or
         # bsort) the forward resolved, reading it; with differentiable edge weights, the
         # graph-only mode the forward resolved
-        grad_sparse = maxk_cuda_kernels.sspmm_backward(
-            indptr, graph_indices, _f32(graph_values), g, sel, row_div=row_div,
-            edge_sel=es if ctx.has_es else None,
-            mode=ctx.es_mode if ctx.has_es else ctx.bwd_mode)
+        if ctx.x16:
+            grad_sparse = maxk_cuda_kernels.sspmm_backward_x16(
+                indptr, graph_indices, _f32(graph_values), g, sel, row_div=row_div)
+        else:
+            grad_sparse = maxk_cuda_kernels.sspmm_backward(
+                indptr, graph_indices, _f32(graph_values), g, sel, row_div=row_div,
+                edge_sel=es if ctx.has_es else None,
+                mode=ctx.es_mode if ctx.has_es else ctx.bwd_mode)
         grads = [None] * ctx.n_inputs
         if ctx.wgrad:
             cbsr_val, fwd_div = ctx.saved_tensors[6:8]
@@ -269,7 +315,9 @@ class MaxKSpGEMMFunction(Function):
             grads[1] = grad_edge.to(graph_values.dtype).reshape(graph_values.shape)
         if ctx.mode == "v1":
             V, D = ctx.shape_v1
-            if ctx.needs_input_grad[2]:
+            if ctx.needs_input_grad[2] and ctx.x16:
+                grads[2] = maxk_cuda_kernels.topk_backward_x16(grad_sparse, None, sel, D)
+            elif ctx.needs_input_grad[2]:
                 grads[2] = maxk_cuda_kernels.cbsr_scatter_dense(grad_sparse, sel, D)
         else:
             grads[2] = grad_sparse
