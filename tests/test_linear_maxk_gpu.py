@@ -14,6 +14,8 @@ import torch
 import linear_maxk_ref as R
 import memguard as M
 import numerics as N
+import topk_rows as TR
+import x16_ref as XR
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +86,48 @@ def test_gaussian_within_bound(mk, shape, bias):
     assert (np.abs(vals - np.take_along_axis(c["h"], idx.astype(np.int64), 1)) <= c["B"]).all()
     srt = np.sort(idx.astype(np.int64), axis=1)
     assert (srt < D).all() and (np.diff(srt, axis=1) > 0).all()
+    assert mk.topk_error_rows() == 0
+
+
+@functools.lru_cache(maxsize=None)
+def hard_case(D, pad):
+    """The finite rows of tests/topk_rows.py as h's rows: W [D, D + pad] is a signed permutation
+    scaled by powers of two (W[d, perm[d]] = +-2^e, e in {-1, 0, 1}, the pad columns zero), so
+    h[v, d] = +-2^e x[v, perm[d]] is one product plus zeros: exact, the same fp32 number in any
+    summation order, and every zero a +0 like the accumulator's.  Rows that a scale takes out of
+    fp32 exactly (a subnormal halved, 3e38 doubled) are left out and named."""
+    rng = np.random.default_rng(5100 + 2 * D + pad)
+    x, names = TR.rows(D, rng, names=True)
+    keep = TR.finite_mask(x)
+    x = np.concatenate([x, rng.standard_normal((len(x), pad), dtype=np.float32)], axis=1)
+    W = np.zeros((D, D + pad), np.float32)
+    W[np.arange(D), rng.permutation(D)] = rng.choice([-1.0, 1.0], D) * 2.0 ** rng.integers(-1, 2, D)
+    h64 = R.hidden(x[keep], W)
+    with np.errstate(over="ignore"):
+        h = h64.astype(np.float32)
+    exact = (h.astype(np.float64) == h64).all(axis=1)
+    skipped = sorted({n.split("/")[0] for n, e in zip(np.array(names)[keep], exact) if not e})
+    h = h[exact] + np.float32(0)  # -0 + 0 = +0
+    assert len(h) >= 30 and not np.signbit(h[h == 0]).any()
+    return dict(x=x[keep][exact], W=W, b=None, h=h, order=XR.topk(h, D)[1], skipped=skipped)
+
+
+@pytest.mark.parametrize("pad", [0, 5])
+@pytest.mark.parametrize("D", [7, 64, 100, 128, 255, 256])
+def test_hard_rows(mk, D, pad):
+    """topk_select.h's copy of the row selection on the corpus the encode's other copies see:
+    values and uint8 columns bitwise against x16_ref.topk at every k of TR.fused_ks; pad = 5
+    adds the K tail (and the scalar loads where I % 4 != 0)."""
+    c = hard_case(D, pad)
+    print(f"D {D} I {D + pad}: {len(c['h'])} rows, left out {c['skipped']}")
+    assert set(c["skipped"]) <= {"steps_subnormal", "huge3e38"}
+    x, W = T(c["x"]), T(c["W"])
+    mk.topk_error_rows()
+    for k in TR.fused_ks(D):
+        idx = c["order"][:, :k]
+        vals, got = mk.linear_maxk_forward(x, W, None, k=k)
+        assert M.same_bytes(vals, T(np.take_along_axis(c["h"], idx, 1))), (D, pad, k)
+        assert M.same_bytes(got, T(idx.astype(np.uint8))), (D, pad, k)
     assert mk.topk_error_rows() == 0
 
 

@@ -54,6 +54,24 @@ def test_range_is_refused(lib, name, D, k):
         assert getattr(lib, name + "_workspace_size")(10, 10, 10, D, k, 0) == 0
 
 
+@pytest.mark.parametrize("D", [7, 100, 256])
+def test_reference_ranking_matches_oracle(D):
+    """x16_ref.topk, the reference of the hard-row tests (tests/topk_rows.py), against the C
+    oracle where the oracle reaches: values and columns bitwise, at every k of the sweep."""
+    import numpy as np
+
+    import oracle as O
+    import topk_rows as TR
+    import x16_ref as XR
+    x, names = TR.rows(D, np.random.default_rng(5000 + D), names=True)
+    assert len(names) == len(x) >= 48 and len(TR.finite(x)) >= 30
+    for k in TR.x16_ks(D):
+        val, idx = XR.topk(x, k)
+        oval, oidx = O.topk(x, k)
+        assert np.array_equal(idx, oidx.astype(np.int64)), (D, k)
+        assert np.array_equal(val.view(np.uint32), oval.view(np.uint32)), (D, k)
+
+
 @pytest.mark.parametrize("name", ENTRIES)
 @pytest.mark.parametrize("D,k", [(1024, 256), (257, 1), (7, 7)])
 def test_range_is_accepted(lib, name, D, k):

@@ -10,6 +10,7 @@ import torch
 import memguard as M
 import numerics as N
 import test_gat_attention_gpu as GA
+import topk_rows as TR
 import x16_ref as XR
 from test_parity_gpu import T
 
@@ -95,6 +96,38 @@ def test_encode_bit_exact(mk, cuda, V, D, k):
     assert mk.topk_error_rows(cuda) == 0
 
 
+@pytest.mark.parametrize("D", [7, 100, 256, 257, 384, 512, 513, 1023, 1024])
+def test_encode_hard_rows(mk, cuda, D):
+    """The corpus of tests/topk_rows.py (keys one apart, clusters that need further radix
+    passes, +-0, NaN, +-Inf, few distinct values, ties across columns 64 j / 256 / 512 and at
+    the last column) through x16_topk_kernel at every k of TR.x16_ks: values, int16 columns and
+    the dense row bitwise against x16_ref.topk; up to D = 256 topk_cbsr gives the same bytes;
+    one k also from a column slice of a wider tensor (ld_x > D)."""
+    x = TR.rows(D, np.random.default_rng(5000 + D))
+    xt = T(x, cuda)
+    wide = torch.full((len(x), D + 8), 11.0, device=cuda)
+    wide[:, 3:3 + D] = xt
+    order = XR.topk(x, min(D, 256))[1]  # a prefix of one ranking serves every k
+    ks = TR.x16_ks(D)
+    mk.topk_error_rows(cuda)
+    for k in ks:
+        idx = order[:, :k]
+        val, it = T(np.take_along_axis(x, idx, 1), cuda), T(idx, cuda)
+        want = torch.zeros(len(x), D, device=cuda).scatter_(1, it, val)
+        dense, v2, i2 = mk.topk_cbsr_dense_x16(xt, k)
+        runs = [mk.topk_cbsr_x16(xt, k), (v2, i2)]
+        if k == ks[len(ks) // 2]:
+            runs.append(mk.topk_cbsr_x16(wide[:, 3:3 + D], k))
+        for v, i in runs:
+            assert i.dtype == torch.int16 and M.same_bytes(v, val), (D, k)
+            assert torch.equal(i.long(), it), (D, k)
+        assert M.same_bytes(dense, want), (D, k)
+        if D <= 256:
+            v8, i8 = mk.topk_cbsr(xt, k)
+            assert M.same_bytes(v8, val) and torch.equal(i8.long(), it), (D, k)
+    assert mk.topk_error_rows(cuda) == 0
+
+
 @pytest.mark.parametrize("V,D,k", [(131, 384, 10), (67, 1024, 256)])
 def test_topk_backward(mk, cuda, V, D, k):
     rng = np.random.default_rng(4050 + D)
@@ -162,6 +195,37 @@ def test_marker_collision(mk, cuda):
         got = run_bwd(mk, c, chunk)
         N.within(got, XR.bwd(g, c["G"], ci), bb[0], f"marker bwd {chunk}")
         assert exact_zero(got, bb[1])
+
+
+@pytest.mark.parametrize("name,D,k", [("S", 384, 16), ("S", 1024, 256), ("R", 257, 3)],
+                         ids=["S-D384-k16", "S-D1024-k256", "R-D257-k3"])
+def test_non_finite(mk, cuda, name, D, k):
+    """numerics.poison's Inf / NaN plan (it works unchanged on selectors above 256 columns)
+    through x16_pack_kernel's folding, x16_fwd_kernel and x16_bwd_kernel, at both item sizes.
+    poison plants its selector >= D only below D = 256, so one more vertex of the hub row gets
+    selector D in one slot and 0xffff (-1 as int16) in another, NaN the value of both: neither
+    contributes forward, both read exactly 0 backward.  The NaN / +Inf / -Inf masks equal the
+    float64 reference's, the finite rest is inside the bound over the finite terms."""
+    c = case(name, D, k, "unit")
+    g = c["g"]
+    cv, ci, G, where = N.poison(g, c["cv"], c["ci"], c["G"], D)
+    hubcols = g.col[g.rp[g.hub]:g.rp[g.hub + 1]]
+    v = int(next(x for x in hubcols if x not in where["verts"] and x != g.unread))
+    ci[v, k - 2], ci[v, k - 1] = D, 0xFFFF
+    cv[v, k - 2:] = np.nan
+    fwd, (fb, fn) = XR.fwd(g, cv, ci, D), XR.bound_fwd(g, cv, ci, D)
+    bwd, (bb, bn) = XR.bwd(g, G, ci), XR.bound_bwd(g, G, ci)
+    print(f"non-finite share: fwd {N.reference_is_meaningful(fwd):.3%}, "
+          f"bwd {N.reference_is_meaningful(bwd):.3%}")
+    assert np.isfinite(fb).all() and np.isfinite(bb).all()
+    assert (bwd[v, k - 2:] == 0).all() and (bn[v, k - 2:] == 0).all()
+    for chunk in (0, 64):
+        out = run_fwd(mk, c, chunk, cv=cv, ci=ci)
+        N.within(out, fwd, fb, f"non-finite fwd {name} D{D} k{k} chunk {chunk}")
+        assert exact_zero(out, fn)
+        got = run_bwd(mk, c, chunk, G=G, ci=ci)
+        N.within(got, bwd, bb, f"non-finite bwd {name} D{D} k{k} chunk {chunk}")
+        assert exact_zero(got, bn)
 
 
 # ------------------------------------------------------------------------------- memory

@@ -29,28 +29,32 @@ def scatter(cv, ci, D):
     X = np.zeros((cv.shape[0], D))
     rows = np.broadcast_to(np.arange(cv.shape[0])[:, None], ci.shape)
     ok = ci < D
-    np.add.at(X, (rows[ok], ci[ok]), cv[ok].astype(np.float64))
+    with np.errstate(invalid="ignore"):
+        np.add.at(X, (rows[ok], ci[ok]), cv[ok].astype(np.float64))
     return X
 
 
 def fwd(g, cv, ci, D):
     X = scatter(cv, ci.astype(np.int64), D)
     out = np.zeros((g.R, D))
-    for r in range(g.R):
-        e = slice(g.rp[r], g.rp[r + 1])
-        out[r] = g.ev[e].astype(np.float64) @ X[g.col[e]] / g.div[r]
+    with np.errstate(invalid="ignore"):  # Inf - Inf is a NaN the kernels give too
+        for r in range(g.R):
+            e = slice(g.rp[r], g.rp[r + 1])
+            out[r] = g.ev[e].astype(np.float64) @ X[g.col[e]] / g.div[r]
     return out
 
 
 def bwd(g, G, ci):
-    Gd = G / g.div[:, None].astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        Gd = G / g.div[:, None].astype(np.float64)
     order = np.argsort(g.col, kind="stable")
     rows = np.repeat(np.arange(g.R), np.diff(g.rp))[order]
     ptr = np.searchsorted(g.col[order], np.arange(g.C + 1))
     Y = np.zeros((g.C, G.shape[1]))  # A^T . (G / row_div)
-    for c in range(g.C):
-        e = slice(ptr[c], ptr[c + 1])
-        Y[c] = g.ev[order[e]].astype(np.float64) @ Gd[rows[e]]
+    with np.errstate(invalid="ignore"):
+        for c in range(g.C):
+            e = slice(ptr[c], ptr[c + 1])
+            Y[c] = g.ev[order[e]].astype(np.float64) @ Gd[rows[e]]
     ci = ci.astype(np.int64)
     ok = ci < G.shape[1]
     return np.where(ok, np.take_along_axis(Y, np.where(ok, ci, 0), 1), 0.0)
@@ -61,11 +65,11 @@ def _unit(g):
 
 
 def bound_fwd(g, cv, ci, D):
-    """(bound, n) of the forward's elements."""
+    """(bound, n) of the forward's elements; S_abs over the finite terms, as in numerics.py."""
     n = fwd(_unit(g), np.ones(cv.shape, np.float32), ci, D)
-    return N._bound(n, fwd(g, np.abs(cv), ci, D), 0.0), n
+    return N._bound(n, fwd(g, N._finite_abs(cv), ci, D), 0.0), n
 
 
 def bound_bwd(g, G, ci):
     n = bwd(_unit(g), np.ones(G.shape, np.float32), ci)
-    return N._bound(n, bwd(g, np.abs(G), ci), 0.0), n
+    return N._bound(n, bwd(g, N._finite_abs(G), ci), 0.0), n
