@@ -1458,6 +1458,60 @@ int maxk_sspmm_backward_x16(const int32_t *row_ptr, const int32_t *col_idx, cons
                             size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * x16 max aggregation (x16_max.hip): maxk_spgemm_max_forward / _backward above
+ * for features of up to 1024 columns, on uint16_t selectors.  1 <= dim_origin <= 1024 and
+ * 1 <= dim_k <= min(dim_origin, 256), anything else refused with MAXK_ERR_INVALID and a message
+ * naming the range; dim_origin <= 256 is served too, with the same bytes of out and arg as the
+ * u8 entries give.  The rules are theirs, word for word: candidates in CSR order, a repeated
+ * selector folded into its first occurrence (fp32 sum in l order), a selector >= dim_origin no
+ * candidate, the first largest candidate wins under strict >, the implicit +0.0 of a neighbour
+ * that does not keep the column competes, a NaN wins and the first NaN stays, out carries the
+ * winner's bits, arg the winning CSR edge or -1, arg == NULL stores no winners.  Bit 0x100 of a
+ * selector is a column like any other.  out and arg are bitwise independent of chunk_edges, of
+ * where a hub row is cut and of what the workspace held.  Empty problems are valid: num_e == 0
+ * writes out = 0 and arg = -1 (grad_cbsr = 0 in the backward).
+ *
+ * maxk_spgemm_max_forward_x16.  workspace, every part rounded up to 256 B:
+ *   num_cols * RS              one packed record [k f32 | k u16 | pad] per column; RS = 6 * dim_k
+ *                              rounded up to a power of two (>= 16) up to 128 B, to 64 B past it;
+ *                              the table must stay below 4 GiB
+ *   + cap * 2 * 8 * dim_origin two rows of 64-bit keys per work item (16 KB at 1024 columns)
+ *   + 2 * (cap * 4)            the rows the items' slabs belong to
+ * cap = ceil((num_rows + num_e) / chunk_edges) (at least 1) for chunk_edges > 0.  chunk_edges = 0
+ * sizes the items itself: about eight per resident wave slot, within [64, 2048] tokens, until
+ * the key rows would exceed max(the record table, 32 MiB); from there the items grow, so the
+ * key rows never exceed that.  The query is non-decreasing in num_e.
+ *
+ * maxk_spgemm_max_backward_x16: the two-phase csc form.  Phase 1 stores one contribution row per
+ * edge, T[e, l] = grad_out[r, s] where s = cbsr_idx[c, l] < dim_origin and arg[r, s] == e, else an
+ * exact 0 (a select: a NaN of grad_out whose arg names another edge or -1 reaches nothing);
+ * phase 2 is maxk_sspmm_backward_csc's, the rows summed per destination in CSC slot order.  No
+ * atomics, bitwise repeatable, every element of grad_cbsr written.  Against
+ * maxk_spgemm_max_backward the sign of a zero sum may differ (explicit zeros are added).
+ * chunk_edges: tokens per work item of both phases, 0 = auto.  col_ptr / csc_eid:
+ * maxk_transpose_plan's.  workspace: as maxk_sspmm_backward_x16 -- (num_e + 1) * dim_k floats of
+ * contribution rows plus phase 2's slabs.
+ * ------------------------------------------------------------------------- */
+size_t maxk_spgemm_max_forward_x16_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                  int64_t num_e, int32_t dim_origin,
+                                                  int32_t dim_k, int32_t chunk_edges);
+int maxk_spgemm_max_forward_x16(const int32_t *row_ptr, const int32_t *col_idx,
+                                const float *cbsr_val, const uint16_t *cbsr_idx, float *out,
+                                int32_t *arg, int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                int32_t dim_origin, int32_t dim_k, int32_t chunk_edges,
+                                void *workspace, size_t workspace_bytes, void *stream);
+size_t maxk_spgemm_max_backward_x16_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                   int64_t num_e, int32_t dim_origin,
+                                                   int32_t dim_k, int32_t chunk_edges);
+int maxk_spgemm_max_backward_x16(const int32_t *row_ptr, const int32_t *col_idx,
+                                 const int32_t *col_ptr, const int32_t *csc_eid,
+                                 const uint16_t *cbsr_idx, const int32_t *arg,
+                                 const float *grad_out, float *grad_cbsr, int64_t num_rows,
+                                 int64_t num_cols, int64_t num_e, int32_t dim_origin,
+                                 int32_t dim_k, int32_t chunk_edges, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * warp4 schedule (drop-in for kernels/generate_meta.py:30-48 / generate_meta_csc.py:14-93
  * and the .warp4 files read by load_warp4_metadata, cuda_kernel_bindings.cpp:287-317).
  * maxk_warp4_count: synchronous; number of entries W = sum over rows of ceil(deg/warp_max_nz).

@@ -63,6 +63,7 @@ __all__ = [
     "pull_stream_plan", "pull_stream_buckets", "PullStreamPlan",
     "topk_cbsr_x16", "topk_cbsr_dense_x16", "topk_backward_x16", "spgemm_forward_x16",
     "sspmm_backward_x16", "MAX_DIM_X16",
+    "spgemm_max_forward_x16", "spgemm_max_backward_x16",
 ]
 
 FULL_DIM = 256  # the reference binding's fixed output width (cuda_kernel_bindings.cpp:70)
@@ -2397,6 +2398,61 @@ def sspmm_backward_x16(indptr: torch.Tensor, indices: torch.Tensor, values: torc
                (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(grad_output), _ptr(cbsr_idx),
                 _ptr(row_div), _ptr(col_ptr), _ptr(csc_eid), _ptr(out), *shape))
     return out
+
+
+def spgemm_max_forward_x16(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
+                           idx: torch.Tensor, dim: int, chunk: int = 0, want_arg: bool = True,
+                           validate: Optional[bool] = None):
+    """spgemm_max_forward on int16 selectors, dim <= MAX_DIM_X16, k <= 256
+    (maxk_spgemm_max_forward_x16): (out [num_rows, dim] float32, arg [num_rows, dim] int32 or
+    None) under the same rules, bitwise independent of `chunk`; at dim <= 256 the same bytes as
+    spgemm_max_forward gives on the uint8 selectors."""
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (vals, "input_data", torch.float32), (idx, "sparse_selector", torch.int16)):
+        _need(t, n, dt)
+    if vals.dim() != 2 or idx.shape != vals.shape:
+        raise RuntimeError("input_data and sparse_selector must have the same [V, k] shape")
+    num_cols, k = vals.shape
+    D = int(dim)
+    num_rows = indptr.numel() - 1
+    _validate_call(validate, indptr, indices, num_cols, idx, D)
+    dev = vals.device
+    out = torch.empty(num_rows, D, dtype=torch.float32, device=dev)
+    arg = torch.empty(num_rows, D, dtype=torch.int32, device=dev) if want_arg else None
+    shape = (num_rows, num_cols, indices.numel(), D, k, int(chunk))
+    _launch_ws(dev, "maxk_spgemm_max_forward_x16", "maxk_spgemm_max_forward_x16_workspace_size",
+               shape, (_ptr(indptr), _ptr(indices), _ptr(vals), _ptr(idx), _ptr(out), _ptr(arg),
+                       *shape))
+    return out, arg
+
+
+def spgemm_max_backward_x16(indptr: torch.Tensor, indices: torch.Tensor, idx: torch.Tensor,
+                            arg: torch.Tensor, grad_out: torch.Tensor, k: int, chunk: int = 0,
+                            plan=None) -> torch.Tensor:
+    """spgemm_max_backward on int16 selectors, grad_out [num_rows, D] with D <= MAX_DIM_X16
+    (maxk_spgemm_max_backward_x16, the two-phase csc form): slot (c, l) receives
+    grad_out[r, idx[c, l]] of every edge (r <- c) that won its column, summed in CSC slot order;
+    bitwise repeatable.  plan: transpose_plan's (col_ptr, csc_eid), from its cache when None."""
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (idx, "sparse_selector", torch.int16), (arg, "arg", torch.int32),
+                     (grad_out, "grad_out", torch.float32)):
+        _need(t, n, dt)
+    k = int(k)
+    if idx.dim() != 2 or idx.shape[1] != k:
+        raise RuntimeError("sparse_selector must be [num_cols, k]")
+    num_cols = idx.shape[0]
+    num_rows = indptr.numel() - 1
+    if grad_out.dim() != 2 or grad_out.shape[0] != num_rows or arg.shape != grad_out.shape:
+        raise RuntimeError("arg and grad_out must be [num_rows, dim_origin]")
+    D = grad_out.shape[1]
+    dev = grad_out.device
+    col_ptr, csc_eid = plan if plan is not None else transpose_plan(indices, num_cols)
+    grad_vals = torch.empty(num_cols, k, dtype=torch.float32, device=dev)
+    shape = (num_rows, num_cols, indices.numel(), D, k, int(chunk))
+    _launch_ws(dev, "maxk_spgemm_max_backward_x16", "maxk_spgemm_max_backward_x16_workspace_size",
+               shape, (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(idx),
+                       _ptr(arg), _ptr(grad_out), _ptr(grad_vals), *shape))
+    return grad_vals
 
 
 def generate_sparse_selector(num_v: int, dim_origin: int, dim_sparse: int) -> torch.Tensor:

@@ -93,7 +93,8 @@ class CSRGraph:
     def aggregate_max(self, topk_values, topk_indices, dim: int):
         """[V, dim]: the element-wise maximum over each row's neighbours of scatter(CBSR)
         (maxk_spgemm_max): a neighbour that does not keep a column competes with 0 there, a row
-        without edges is 0.  Unweighted: the graph's edge values are not used."""
+        without edges is 0.  Unweighted: the graph's edge values are not used.  dim up to 1024:
+        past 256 columns, or on int16 indices, the 16-bit-selector kernels run."""
         return maxk_spgemm_max(self.indptr, self.indices, topk_values, topk_indices, dim)
 
     def aggregate_heads(self, topk_values, topk_indices, dim: int, values, row_div=None):

@@ -732,7 +732,9 @@ class MaxKSpGEMMMaxFunction(Function):
     apply(graph_indptr, graph_indices, topk_values [V, k], topk_indices [V, k], dim_origin)
     -> out [V, dim_origin] (maxk_cuda_kernels.spgemm_max_forward has the rules: the first
     largest candidate in edge order wins, a neighbour that does not keep a column competes with
-    an implicit zero, a NaN beats everything).
+    an implicit zero, a NaN beats everything).  dim_origin > 256 or int16 topk_indices take
+    spgemm_max_forward_x16 / spgemm_max_backward_x16 (up to 1024 columns, k <= 256), the rule of
+    MaxKSpGEMMFunction._forward_v4; anything else the uint8 pair, as before.
 
     The forward saves the winners' edge indices arg [V, dim_origin] int32 and topk_indices, and
     nothing else of the activations (the graph's own tensors ride on the context); when
@@ -746,11 +748,17 @@ class MaxKSpGEMMMaxFunction(Function):
                 grad_mode=True):
         _require_kernels()
         indptr, indices = _i32(graph_indptr), _i32(graph_indices)
-        sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
-        sel = sel.contiguous()
         want = bool(grad_mode and ctx.needs_input_grad[2])
-        out, arg = maxk_cuda_kernels.spgemm_max_forward(indptr, indices, _f32_act(topk_values),
-                                                        sel, int(dim_origin), want_arg=want)
+        if topk_indices.dtype == torch.int16 or int(dim_origin) > FULL_DIM:
+            sel = _sel16(topk_indices)  # the x16 pair: up to 1024 columns
+            out, arg = maxk_cuda_kernels.spgemm_max_forward_x16(
+                indptr, indices, _f32_act(topk_values), sel, int(dim_origin), want_arg=want)
+        else:
+            sel = (topk_indices if topk_indices.dtype == torch.uint8
+                   else topk_indices.to(torch.uint8))
+            sel = sel.contiguous()
+            out, arg = maxk_cuda_kernels.spgemm_max_forward(
+                indptr, indices, _f32_act(topk_values), sel, int(dim_origin), want_arg=want)
         if want:
             ctx.graph = (indptr, indices)
             ctx.val_dtype = topk_values.dtype
@@ -761,8 +769,9 @@ class MaxKSpGEMMMaxFunction(Function):
     def backward(ctx, grad_output):
         arg, sel = ctx.saved_tensors
         indptr, indices = ctx.graph
-        grad = maxk_cuda_kernels.spgemm_max_backward(indptr, indices, sel, arg,
-                                                     _f32_grad(grad_output), sel.shape[1])
+        bwd = (maxk_cuda_kernels.spgemm_max_backward_x16 if sel.dtype == torch.int16
+               else maxk_cuda_kernels.spgemm_max_backward)
+        grad = bwd(indptr, indices, sel, arg, _f32_grad(grad_output), sel.shape[1])
         return None, None, grad.to(ctx.val_dtype), None, None, None
 
 
