@@ -1512,6 +1512,81 @@ int maxk_spgemm_max_backward_x16(const int32_t *row_ptr, const int32_t *col_idx,
                                  size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * x16 multi-head aggregation (x16_heads.hip): maxk_spgemm_forward_heads,
+ * maxk_edge_weight_grad_heads and maxk_sspmm_backward_heads above for features of up to 1024
+ * columns, on uint16_t selectors -- what the stored attention path of the GAT and transformer
+ * layers runs past 256 columns.  1 <= dim_origin <= 1024, 1 <= dim_k <= min(dim_origin, 256),
+ * 1 <= num_heads <= MAXK_MAX_HEADS, anything else refused with MAXK_ERR_INVALID and a message
+ * naming the range (the workspace queries then return 0); dim_origin <= 256 is served too.
+ * Layout, head-major as there: edge_val, grad_edge [num_heads, num_e]; out, grad_out
+ * [num_heads, num_rows, dim_origin]; row_div [num_rows] shared by the heads, or NULL.
+ * The rules of all three: fp32; no global atomics and no LDS float atomics; every sum in an order
+ * fixed by (graph, chunk_edges, dim_k, dim_origin, num_heads), so results are bitwise repeatable
+ * and each element is within (n + 8) * 2^-24 * sum|terms| of exact arithmetic; repeated
+ * selectors of a CBSR row accumulate, selectors >= dim_origin are ignored; inputs are never
+ * written; the workspace is exactly the queried size, 256-B aligned, and may hold anything;
+ * num_e == 0 and num_rows == 0 are valid; a packed record table of 4 GiB or more
+ * (num_cols * record stride, as maxk_spgemm_forward_x16) is refused.
+ *
+ * maxk_spgemm_forward_heads_x16:
+ *   out[h, r, cbsr_idx[c,l]] += edge_val[h, e] * cbsr_val[c,l] / row_div[r]
+ * every row of every head written (rows without edges get zeros).  The record of a column is
+ * gathered once per edge and pass of min(num_heads, C) heads, C the output copies a wave keeps:
+ * 4 up to dim_origin = 508, 2 up to 1024, 1 when dim_k > 32.  Head h's slice holds only
+ * products with head h's weights and does not depend, bitwise, on the other heads' weights.
+ * workspace: the packed records, a slab row of dim_origin floats per head and work item, and a
+ * row index per work item.
+ *
+ * maxk_edge_weight_grad_heads_x16:
+ *   grad_edge[h, e] = ( sum_l cbsr_val[c,l] * grad_out[h, r, cbsr_idx[c,l]] ) / row_div[r]
+ * grad_edge fully written; an edge whose column keeps no selector below dim_origin gets exactly
+ * 0; a NaN in a column of grad_out that the vertex does not select, or in another head's
+ * grad_out, reaches nothing.  workspace: the packed records.
+ *
+ * maxk_sspmm_backward_heads_x16:
+ *   grad_cbsr[c,l] = sum_h sum_{e=(r->c)} edge_val[h,e] * grad_out[h,r,cbsr_idx[c,l]] / row_div[r]
+ * as the two-phase csc form: phase 1 sums the heads per edge in head order and stores one
+ * contribution row, phase 2 is maxk_sspmm_backward_csc's.  Every element of grad_cbsr written, a
+ * column without in-edges exactly 0, a selector >= dim_origin contributes 0.  At num_heads == 1
+ * the result equals maxk_sspmm_backward_x16's bitwise.  col_ptr / csc_eid: maxk_transpose_plan's.
+ * workspace: as maxk_sspmm_backward_x16.
+ * ------------------------------------------------------------------------- */
+size_t maxk_spgemm_forward_heads_x16_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                    int64_t num_e, int32_t dim_origin,
+                                                    int32_t dim_k, int32_t num_heads,
+                                                    int32_t chunk_edges);
+int maxk_spgemm_forward_heads_x16(const int32_t *row_ptr, const int32_t *col_idx,
+                                  const float *edge_val, const float *cbsr_val,
+                                  const uint16_t *cbsr_idx, const float *row_div, float *out,
+                                  int64_t num_rows, int64_t num_cols, int64_t num_e,
+                                  int32_t dim_origin, int32_t dim_k, int32_t num_heads,
+                                  int32_t chunk_edges, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+size_t maxk_edge_weight_grad_heads_x16_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                      int64_t num_e, int32_t dim_origin,
+                                                      int32_t dim_k, int32_t num_heads,
+                                                      int32_t chunk_edges);
+int maxk_edge_weight_grad_heads_x16(const int32_t *row_ptr, const int32_t *col_idx,
+                                    const float *cbsr_val, const uint16_t *cbsr_idx,
+                                    const float *grad_out, const float *row_div,
+                                    float *grad_edge, int64_t num_rows, int64_t num_cols,
+                                    int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                                    int32_t num_heads, int32_t chunk_edges, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+size_t maxk_sspmm_backward_heads_x16_workspace_size(int64_t num_rows, int64_t num_cols,
+                                                    int64_t num_e, int32_t dim_origin,
+                                                    int32_t dim_k, int32_t num_heads,
+                                                    int32_t chunk_edges);
+int maxk_sspmm_backward_heads_x16(const int32_t *row_ptr, const int32_t *col_idx,
+                                  const float *edge_val, const float *grad_out,
+                                  const float *row_div, const uint16_t *cbsr_idx,
+                                  const int32_t *col_ptr, const int32_t *csc_eid,
+                                  float *grad_cbsr, int64_t num_rows, int64_t num_cols,
+                                  int64_t num_e, int32_t dim_origin, int32_t dim_k,
+                                  int32_t num_heads, int32_t chunk_edges, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * warp4 schedule (drop-in for kernels/generate_meta.py:30-48 / generate_meta_csc.py:14-93
  * and the .warp4 files read by load_warp4_metadata, cuda_kernel_bindings.cpp:287-317).
  * maxk_warp4_count: synchronous; number of entries W = sum over rows of ceil(deg/warp_max_nz).

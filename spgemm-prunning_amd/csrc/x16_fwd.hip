@@ -79,6 +79,22 @@ __global__ __launch_bounds__(kX16PackBlock) void x16_pack_kernel(
     }
 }
 
+}  // namespace
+
+int launch_x16_pack(const float *cbsr_val, const uint16_t *cbsr_idx, uint8_t *rec, int64_t num_cols,
+                    int k, int RS, int D, int trash, hipStream_t s) {
+    const int vpb = kX16PackBlock / k < kX16PackMaxV ? kX16PackBlock / k : kX16PackMaxV;
+    const int64_t groups = ceil_div(num_cols, (int64_t)vpb);
+    hipLaunchKernelGGL(x16_pack_kernel,
+                       dim3((unsigned)(groups < MAXK_PACK_GRID ? groups : MAXK_PACK_GRID)),
+                       dim3(kX16PackBlock), 0, s, cbsr_val, cbsr_idx, rec, (int)num_cols, k, RS, D,
+                       trash);
+    MAXK_LAUNCHED("x16_pack_kernel");
+    return MAXK_OK;
+}
+
+namespace {
+
 // acc_g[column] += val[e] * value over the edges [sb, se), sb < se; acc_g is the copy of this
 // lane's edge group.  Lanes past k, and edges past se (the descriptors return column 0, weight
 // 0), write the trash column: two lanes of a group never share a live address in one ds_write,
@@ -290,15 +306,9 @@ extern "C" int maxk_spgemm_forward_x16(const int32_t *row_ptr, const int32_t *co
     float *slab = reinterpret_cast<float *>(ws + L.slab_off);
     int32_t *slab_row = reinterpret_cast<int32_t *>(ws + L.row_off);
     hipStream_t s = as_stream(stream);
-    if (num_cols > 0 && num_e > 0) {
-        const int vpb = kX16PackBlock / k < kX16PackMaxV ? kX16PackBlock / k : kX16PackMaxV;
-        const int64_t groups = ceil_div(num_cols, (int64_t)vpb);
-        hipLaunchKernelGGL(x16_pack_kernel,
-                           dim3((unsigned)(groups < MAXK_PACK_GRID ? groups : MAXK_PACK_GRID)),
-                           dim3(kX16PackBlock), 0, s, cbsr_val, cbsr_idx, rec, (int)num_cols, k,
-                           L.RS, D, L.DS - 1);
-        MAXK_LAUNCHED("x16_pack_kernel");
-    }
+    if (num_cols > 0 && num_e > 0)
+        if (int rc = launch_x16_pack(cbsr_val, cbsr_idx, rec, num_cols, k, L.RS, D, L.DS - 1, s))
+            return rc;
     const int vec = D % 4 == 0 && ((uintptr_t)out & 15) == 0;
     const bool ok = with_const<16, 32, 64>(L.kg, [&](auto kg_c) {
         constexpr int KG = decltype(kg_c)::value;

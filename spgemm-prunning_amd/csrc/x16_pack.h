@@ -1,6 +1,6 @@
-// What the x16 kernels share (x16_topk.hip, x16_fwd.hip, x16_bwd.hip): the shape range of the
-// 16-bit-selector path, its packed record (packed by x16_fwd.hip's x16_pack_kernel), the LDS
-// row stride and the item size rule.  DESIGN.md 5.20.
+// What the x16 kernels share (x16_topk.hip, x16_fwd.hip, x16_bwd.hip, x16_heads.hip): the shape
+// range of the 16-bit-selector path, its packed record (packed by x16_fwd.hip's x16_pack_kernel,
+// launched through launch_x16_pack), the LDS row stride and the item size rule.  DESIGN.md 5.20.
 //
 // Record of one source vertex: [k f32 values | k u16 columns | pad], RS bytes.  The u16 is the LDS
 // column the walker accumulates into: the selector itself when it is kept, else the trash column
@@ -50,6 +50,17 @@ inline int x16_lanes(int k, int lo) {
     int g = lo;
     while (g < k && g < kWave) g <<= 1;
     return g;
+}
+
+// x16_pack_kernel (x16_fwd.hip) on the stream: rec[v] = vertex v's record, num_cols > 0.
+int launch_x16_pack(const float *cbsr_val, const uint16_t *cbsr_idx, uint8_t *rec, int64_t num_cols,
+                    int k, int RS, int D, int trash, hipStream_t s);
+
+// Dense rows of DS floats a wave stages side by side in the budget of the forward's copies, about
+// 8 KB: 2 at D = 1024, 4 at D = 508, more for narrower rows, at most MAXK_MAX_HEADS (x16_heads.hip).
+inline int x16_rows_in_budget(int DS) {
+    const int n = 2056 / DS;
+    return n < 2 ? 2 : (n > MAXK_MAX_HEADS ? MAXK_MAX_HEADS : n);
 }
 
 // Auto item size: about eight items per resident wave slot (16 slots per CU assumed: the LDS

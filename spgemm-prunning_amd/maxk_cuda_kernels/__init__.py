@@ -64,6 +64,7 @@ __all__ = [
     "topk_cbsr_x16", "topk_cbsr_dense_x16", "topk_backward_x16", "spgemm_forward_x16",
     "sspmm_backward_x16", "MAX_DIM_X16",
     "spgemm_max_forward_x16", "spgemm_max_backward_x16",
+    "spgemm_forward_heads_x16", "edge_weight_grad_heads_x16", "sspmm_backward_heads_x16",
 ]
 
 FULL_DIM = 256  # the reference binding's fixed output width (cuda_kernel_bindings.cpp:70)
@@ -416,7 +417,9 @@ def heads_forward_route(num_rows: int, num_e: int) -> str:
     calls; "calls", H spgemm_forward calls into the slices of one output, on a dense one, whose
     records stay in the caches -- Reddit-sized, k = 16: 1.00 and 0.99, inside the run-to-run
     spread (profiles/r12/heads/).  The weight gradient takes
-    edge_weight_grad_heads everywhere (0.52 to 0.62).  MAXK_HEADS_FWD=heads|calls forces one."""
+    edge_weight_grad_heads everywhere (0.52 to 0.62).  MAXK_HEADS_FWD=heads|calls forces one.
+    Measured for the uint8 kernels only: the x16 path (int16 selectors or dim_origin > 256) does
+    not ask this rule, its forward is always spgemm_forward_heads_x16."""
     forced = os.environ.get("MAXK_HEADS_FWD", "")
     if forced in ("heads", "calls"):
         return forced
@@ -1978,7 +1981,9 @@ def heads_backward_route(k: int, num_e: int, num_cols: int, num_rows: int,
     num_heads == 1, when given, returns "calls".
     "calls" also for a table the multi-head entry rejects (HEADS_MAX_COLS columns or more) and,
     unless MAXK_HEADS_BWD=heads|calls forces a route, when MAXK_BWD_MODE forces a backward mode
-    (graph_only_mode returns None: the forced mode is what the H calls then run)."""
+    (graph_only_mode returns None: the forced mode is what the H calls then run).
+    Measured for the uint8 kernels only: the x16 path (int16 selectors or dim_origin > 256) does
+    not ask this rule, its feature backward is always sspmm_backward_heads_x16."""
     if num_cols >= HEADS_MAX_COLS:
         return "calls"
     forced = os.environ.get("MAXK_HEADS_BWD", "")
@@ -2453,6 +2458,118 @@ def spgemm_max_backward_x16(indptr: torch.Tensor, indices: torch.Tensor, idx: to
                shape, (_ptr(indptr), _ptr(indices), _ptr(col_ptr), _ptr(csc_eid), _ptr(idx),
                        _ptr(arg), _ptr(grad_out), _ptr(grad_vals), *shape))
     return grad_vals
+
+
+def _heads_operands_x16(indptr, indices, cbsr_val, cbsr_idx, row_div, validate, D):
+    """_heads_operands on int16 selectors; cbsr_val is None where the call takes no values.
+    Returns (num_rows, num_cols, k)."""
+    for t, n, dt in ((indptr, "indptr", torch.int32), (indices, "indices", torch.int32),
+                     (cbsr_idx, "sparse_selector", torch.int16)):
+        _need(t, n, dt)
+    if cbsr_idx.dim() != 2:
+        raise RuntimeError("sparse_selector must be [V, k]")
+    if cbsr_val is not None:
+        _need(cbsr_val, "input_data", torch.float32)
+        if cbsr_idx.shape != cbsr_val.shape:
+            raise RuntimeError("input_data and sparse_selector must have the same [V, k] shape")
+    num_cols, k = cbsr_idx.shape
+    num_rows = indptr.numel() - 1
+    if row_div is not None:
+        _need(row_div, "row_div", torch.float32)
+        if row_div.numel() != num_rows:
+            raise RuntimeError("row_div must have num_rows entries")
+    _validate_call(validate, indptr, indices, num_cols, cbsr_idx, D)
+    return num_rows, num_cols, k
+
+
+def spgemm_forward_heads_x16(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
+                             cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor, dim_origin: int,
+                             row_div: Optional[torch.Tensor] = None, chunk: int = 0,
+                             out: Optional[torch.Tensor] = None,
+                             validate: Optional[bool] = None) -> torch.Tensor:
+    """spgemm_forward_heads on int16 selectors, dim_origin <= MAX_DIM_X16, k <= 256
+    (maxk_spgemm_forward_heads_x16): out[H, num_rows, D] for the H weight sets values [H, E], a
+    column's record gathered once per edge and pass of heads.  Head h's slice is, within the
+    forward's bound, spgemm_forward_x16(..., values[h], ...), and does not depend on the other
+    heads' weights; bitwise repeatable."""
+    D = int(dim_origin)
+    _need(values, "values", torch.float32)
+    num_rows, num_cols, k = _heads_operands_x16(indptr, indices, cbsr_val, cbsr_idx, row_div,
+                                                validate, D)
+    E = indices.numel()
+    if values.dim() != 2 or values.shape[1] != E or not 1 <= values.shape[0] <= MAX_HEADS:
+        raise RuntimeError(f"values must be [H, num_e] with 1 <= H <= {MAX_HEADS}")
+    H = values.shape[0]
+    dev = cbsr_val.device
+    out = _heads_out(out, (H, num_rows, D), dev, "[H, num_rows, dim_origin]")
+    shape = (num_rows, num_cols, E, D, k, H, chunk)
+    _launch_ws(dev, "maxk_spgemm_forward_heads_x16", "maxk_spgemm_forward_heads_x16_workspace_size",
+               shape, (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(cbsr_val), _ptr(cbsr_idx),
+                       _ptr(row_div), _ptr(out), *shape))
+    return out
+
+
+def edge_weight_grad_heads_x16(indptr: torch.Tensor, indices: torch.Tensor,
+                               cbsr_val: torch.Tensor, cbsr_idx: torch.Tensor,
+                               grad_output: torch.Tensor, row_div: Optional[torch.Tensor] = None,
+                               chunk: int = 0, out: Optional[torch.Tensor] = None,
+                               validate: Optional[bool] = None) -> torch.Tensor:
+    """edge_weight_grad_heads on int16 selectors, grad_output [H, num_rows, D] with
+    D <= MAX_DIM_X16 (maxk_edge_weight_grad_heads_x16): grad_edge[H, E], the adjoint of
+    spgemm_forward_heads_x16 in `values`; bitwise repeatable, head h's slice independent of the
+    other heads' gradients."""
+    _need(grad_output, "grad_output", torch.float32)
+    if grad_output.dim() != 3 or not 1 <= grad_output.shape[0] <= MAX_HEADS:
+        raise RuntimeError(f"grad_output must be [H, num_rows, dim_origin] with 1 <= H <= "
+                           f"{MAX_HEADS}")
+    H, _, D = grad_output.shape
+    num_rows, num_cols, k = _heads_operands_x16(indptr, indices, cbsr_val, cbsr_idx, row_div,
+                                                validate, D)
+    if grad_output.shape[1] != num_rows:
+        raise RuntimeError("grad_output must be [H, num_rows, dim_origin]")
+    E = indices.numel()
+    dev = grad_output.device
+    out = _heads_out(out, (H, E), dev, "[H, num_e]")
+    shape = (num_rows, num_cols, E, D, k, H, chunk)
+    _launch_ws(dev, "maxk_edge_weight_grad_heads_x16",
+               "maxk_edge_weight_grad_heads_x16_workspace_size", shape,
+               (_ptr(indptr), _ptr(indices), _ptr(cbsr_val), _ptr(cbsr_idx), _ptr(grad_output),
+                _ptr(row_div), _ptr(out), *shape))
+    return out
+
+
+def sspmm_backward_heads_x16(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
+                             grad_output: torch.Tensor, cbsr_idx: torch.Tensor,
+                             row_div: Optional[torch.Tensor] = None, chunk: int = 0,
+                             out: Optional[torch.Tensor] = None, validate: Optional[bool] = None,
+                             plan=None) -> torch.Tensor:
+    """sspmm_backward_heads on int16 selectors, grad_output [H, num_rows, D] with
+    D <= MAX_DIM_X16 (maxk_sspmm_backward_heads_x16): grad_cbsr[num_cols, k], the sum over the
+    heads of sspmm_backward_x16(..., values[h], grad_output[h], ...) with the heads summed per
+    edge before the contribution row is stored; bitwise repeatable, and at H == 1 bitwise that
+    call.  plan: transpose_plan's (col_ptr, csc_eid), taken from its cache when None."""
+    _need(values, "values", torch.float32)
+    _need(grad_output, "grad_output", torch.float32)
+    if grad_output.dim() != 3 or not 1 <= grad_output.shape[0] <= MAX_HEADS:
+        raise RuntimeError(f"grad_output must be [H, num_rows, dim_origin] with 1 <= H <= "
+                           f"{MAX_HEADS}")
+    H, _, D = grad_output.shape
+    num_rows, num_cols, k = _heads_operands_x16(indptr, indices, None, cbsr_idx, row_div,
+                                                validate, D)
+    E = indices.numel()
+    if grad_output.shape[1] != num_rows:
+        raise RuntimeError("grad_output must be [H, num_rows, dim_origin]")
+    if tuple(values.shape) != (H, E):
+        raise RuntimeError("values must be [H, num_e], H that of grad_output")
+    dev = grad_output.device
+    out = _heads_out(out, (num_cols, k), dev, "[num_cols, k]")
+    col_ptr, csc_eid = plan if plan is not None else transpose_plan(indices, num_cols)
+    shape = (num_rows, num_cols, E, D, k, H, chunk)
+    _launch_ws(dev, "maxk_sspmm_backward_heads_x16", "maxk_sspmm_backward_heads_x16_workspace_size",
+               shape, (_ptr(indptr), _ptr(indices), _ptr(values), _ptr(grad_output),
+                       _ptr(row_div), _ptr(cbsr_idx), _ptr(col_ptr), _ptr(csc_eid), _ptr(out),
+                       *shape))
+    return out
 
 
 def generate_sparse_selector(num_v: int, dim_origin: int, dim_sparse: int) -> torch.Tensor:

@@ -234,6 +234,19 @@ SIGNATURES = {
     "maxk_spgemm_max_backward_x16_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32]),
     "maxk_spgemm_max_backward_x16": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64,
                                                     _i64, _i32, _i32, _i32, _p, _sz, _p]),
+    "maxk_spgemm_forward_heads_x16_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32,
+                                                           _i32]),
+    "maxk_spgemm_forward_heads_x16": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
+                                                     _i32, _i32, _i32, _i32, _p, _sz, _p]),
+    "maxk_edge_weight_grad_heads_x16_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32,
+                                                             _i32]),
+    "maxk_edge_weight_grad_heads_x16": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64,
+                                                       _i64, _i32, _i32, _i32, _i32, _p, _sz, _p]),
+    "maxk_sspmm_backward_heads_x16_workspace_size": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32,
+                                                           _i32]),
+    "maxk_sspmm_backward_heads_x16": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64,
+                                                     _i64, _i64, _i32, _i32, _i32, _i32, _p, _sz,
+                                                     _p]),
     "maxk_warp4_count": (ctypes.c_int, [_p, _i64, _i32, ctypes.POINTER(_i64), _p]),
     "maxk_warp4_build_workspace_size": (_sz, [_i64]),
     "maxk_warp4_build": (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _p, _sz, _p]),

@@ -628,6 +628,10 @@ class MaxKGATConv(nn.Module):
     aggregation (its feature backward, edge_weight_grad and the softmax backward).  The
     reference has no GAT: there is no reference_compat.
 
+    in_feats <= 256: the aggregation goes through CSRGraph.aggregate, whose edge-weight gradient
+    has no 16-bit-selector form.  For wider features use MaxKMultiHeadGATConv(num_heads=1), whose
+    stored attention serves in_feats up to 1024.
+
     attn_drop: the GAT's dropout of alpha between the softmax and the aggregation, in training
     mode, through mk.edge_dropout_heads at one head (see MaxKMultiHeadGATConv);
     forward(..., attn_seed=) fixes the mask's seed."""
@@ -668,6 +672,14 @@ class MaxKGATConv(nn.Module):
         return rst
 
 
+def _fused_width(layer, mode: str) -> None:
+    """The fused attention walks take up to 256 columns; the stored path goes on to 1024."""
+    if mode == "fused" and layer.in_feats > 256:
+        raise ValueError(f"{type(layer).__name__}: the fused attention walk takes in_feats <= 256, "
+                         f'got {layer.in_feats}; use attention="stored", which serves in_feats '
+                         f"up to {mk.MAX_DIM_X16}")
+
+
 class MaxKMultiHeadGATConv(nn.Module):
     """GAT with num_heads heads on MaxK features; returns [V, num_heads, out_feats], as the
     usual multi-head GATConv does:
@@ -688,6 +700,10 @@ class MaxKMultiHeadGATConv(nn.Module):
     attention_backward="fused" (with the fused attention only; the default is "rebuilt") runs
     that backward as one walk without alpha (CSRGraph.attend_heads(backward="fused"));
     MAXK_HEADS_ATTN_BWD=fused|rebuilt overrides the argument.
+
+    256 < in_feats <= 1024 (int16 topk_indices from MaxK): the stored attention runs the
+    16-bit-selector multi-head kernels (mk.spgemm_forward_heads_x16 and its two gradients);
+    the fused attention stays at in_feats <= 256 and raises a ValueError past it.
 
     attn_drop: the GAT's attention dropout, in training mode: every alpha_hvu is zeroed with
     probability attn_drop and the kept ones scaled by 1 / (1 - attn_drop), after the softmax's
@@ -750,6 +766,7 @@ class MaxKMultiHeadGATConv(nn.Module):
         v = torch.cat((torch.einsum("hoi,ho->ih", W, self.attn_dst),
                        torch.einsum("hoi,ho->ih", W, self.attn_src)), 1)  # [in, 2H]
         s = (x_sparse @ v).t().contiguous()                               # [2H, V]
+        _fused_width(self, self.attention_mode())
         if self.attention_mode() == "fused":
             agg = graph.attend_heads(topk_values, topk_indices, self.in_feats, s[:H], s[H:],
                                      self.negative_slope, self.attention_backward_mode(), p,
@@ -783,6 +800,9 @@ class MaxKTransformerConv(nn.Module):
     softmax per head and the aggregation over the stored coefficients; attention="fused" runs
     CSRGraph.dot_attend_heads, which keeps the row statistics [H, V] instead and rebuilds alpha
     as a transient in the backward.  MAXK_DOT_ATTN=fused|stored overrides the argument.
+    256 < in_feats <= 1024 (int16 topk_indices from MaxK): the stored attention runs the
+    16-bit-selector multi-head kernels for the scores and the aggregation; the fused attention
+    stays at in_feats <= 256 and raises a ValueError past it.
 
     attention_backward="fused" (with the fused attention only; the default is "rebuilt") runs
     that backward as one mk.dot_attention_heads_backward call, with no [H, E] tensor in the
@@ -845,6 +865,7 @@ class MaxKTransformerConv(nn.Module):
         H, O, I = self.num_heads, self.out_feats, self.in_feats
         p = self.attn_drop if self.training else 0.0
         fused = self.attention_mode() == "fused"
+        _fused_width(self, self.attention_mode())
         if fused and p > 0 and not self.fused_attn_drop:
             raise ValueError("MaxKTransformerConv: the fused walk has no dropout yet; use "
                              'attention="stored" with attn_drop > 0, or opt into the masked '

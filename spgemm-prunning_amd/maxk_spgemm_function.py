@@ -368,7 +368,12 @@ class MaxKSpGEMMHeadsFunction(Function):
     maxk_cuda_kernels.heads_backward_route says "heads": two or more heads, no forced backward
     mode; on route "calls" it is the sum, in head order, of sspmm_backward on (graph_values[h],
     grad_output[h]) in the graph-only mode the single-head function takes with differentiable
-    weights."""
+    weights.
+
+    int16 topk_indices or dim_origin > 256 (up to 1024 columns, k <= 256) take the x16 trio
+    instead, whatever the graph: spgemm_forward_heads_x16, edge_weight_grad_heads_x16 and
+    sspmm_backward_heads_x16.  The two routes above were measured for the uint8 kernels and are
+    not asked there."""
 
     @staticmethod
     def forward(ctx, graph_indptr, graph_indices, graph_values, topk_values, topk_indices,
@@ -376,14 +381,21 @@ class MaxKSpGEMMHeadsFunction(Function):
         _require_kernels()
         indptr, indices = _i32(graph_indptr), _i32(graph_indices)
         vals = _f32_act(topk_values)
-        sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
-        sel = sel.contiguous()
         w = _f32_act(graph_values)  # attention weights change every step: never cached
         row_div = _f32(degrees)
         D = int(dim_origin)
         V, k = vals.shape
         num_rows = indptr.numel() - 1
-        if maxk_cuda_kernels.heads_forward_route(num_rows, indices.numel()) == "heads":
+        ctx.x16 = topk_indices.dtype == torch.int16 or D > FULL_DIM
+        if ctx.x16:
+            sel = _sel16(topk_indices)
+        else:
+            sel = (topk_indices if topk_indices.dtype == torch.uint8
+                   else topk_indices.to(torch.uint8)).contiguous()
+        if ctx.x16:  # the routes below are rules measured for the uint8 kernels
+            out = maxk_cuda_kernels.spgemm_forward_heads_x16(indptr, indices, w, vals, sel, D,
+                                                             row_div=row_div)
+        elif maxk_cuda_kernels.heads_forward_route(num_rows, indices.numel()) == "heads":
             out = maxk_cuda_kernels.spgemm_forward_heads(indptr, indices, w, vals, sel, D,
                                                          row_div=row_div)
         else:  # a dense graph: the multi-head kernel measured no faster there
@@ -409,6 +421,14 @@ class MaxKSpGEMMHeadsFunction(Function):
         if g.dtype != torch.float32:
             g = g.float()
         grad_w = grad_tv = None
+        if ctx.x16:
+            if ctx.needs_input_grad[2]:
+                grad_w = maxk_cuda_kernels.edge_weight_grad_heads_x16(
+                    indptr, indices, vals, sel, g, row_div=row_div).to(ctx.w_dtype)
+            if ctx.needs_input_grad[3]:
+                grad_tv = maxk_cuda_kernels.sspmm_backward_heads_x16(indptr, indices, w, g, sel,
+                                                                     row_div=row_div)
+            return None, None, grad_w, grad_tv, None, None, None
         if ctx.needs_input_grad[2]:
             grad_w = maxk_cuda_kernels.edge_weight_grad_heads(indptr, indices, vals, sel, g,
                                                               row_div=row_div).to(ctx.w_dtype)
@@ -571,11 +591,16 @@ def maxk_gat_attention_heads(graph_indptr, graph_indices, s_dst, s_src, topk_val
                                                negative_slope, backward, dropout, seed)[0]
 
 
-def _dot_inputs(graph_indptr, graph_indices, q, topk_values, topk_indices):
-    """The operands of the dot-product attention functions as the kernels take them."""
-    sel = topk_indices if topk_indices.dtype == torch.uint8 else topk_indices.to(torch.uint8)
-    return (_i32(graph_indptr), _i32(graph_indices), _f32_act(q), _f32_act(topk_values),
-            sel.contiguous())
+def _dot_inputs(graph_indptr, graph_indices, q, topk_values, topk_indices, x16_ok=False):
+    """The operands of the dot-product attention functions as the kernels take them.  x16_ok
+    (the stored scores): int16 selectors, or queries wider than 256 columns, keep the selectors
+    as int16 for the x16 kernels (_sel16); the fused walks take uint8 only."""
+    if x16_ok and (topk_indices.dtype == torch.int16 or q.shape[-1] > FULL_DIM):
+        sel = _sel16(topk_indices)
+    else:
+        sel = (topk_indices if topk_indices.dtype == torch.uint8
+               else topk_indices.to(torch.uint8)).contiguous()
+    return _i32(graph_indptr), _i32(graph_indices), _f32_act(q), _f32_act(topk_values), sel
 
 
 def _f32_grad(g):
@@ -592,31 +617,37 @@ class MaxKDotScoresHeadsFunction(Function):
     edge-weight gradient with the query in the place of grad_out: the forward is
     edge_weight_grad_heads(grad_output=q), the gradient of q is spgemm_forward_heads with the
     logits' gradient as the edge weights, and the gradient of topk_values is
-    sspmm_backward_heads(values=grad, grad_output=q)."""
+    sspmm_backward_heads(values=grad, grad_output=q).  With int16 topk_indices or q wider than
+    256 columns the three are their x16 forms, up to 1024 columns."""
 
     @staticmethod
     def forward(ctx, graph_indptr, graph_indices, q, topk_values, topk_indices, scale):
         _require_kernels()
         indptr, indices, qf, vals, sel = _dot_inputs(graph_indptr, graph_indices, q, topk_values,
-                                                     topk_indices)
+                                                     topk_indices, x16_ok=True)
+        mk = maxk_cuda_kernels
         ctx.scale = float(scale)
         ctx.q_dtype = q.dtype
-        logits = maxk_cuda_kernels.edge_weight_grad_heads(indptr, indices, vals, sel, qf)
+        score = mk.edge_weight_grad_heads_x16 if sel.dtype == torch.int16 \
+            else mk.edge_weight_grad_heads
+        logits = score(indptr, indices, vals, sel, qf)
         ctx.save_for_backward(indptr, indices, qf, vals, sel)
         return logits.mul_(ctx.scale)
 
     @staticmethod
     def backward(ctx, grad_output):
         indptr, indices, qf, vals, sel = ctx.saved_tensors
+        mk = maxk_cuda_kernels
+        x16 = sel.dtype == torch.int16  # the same composition on the x16 trio
         g = _f32_grad(grad_output)
         grad_q = grad_tv = None
         if ctx.needs_input_grad[2]:
-            grad_q = maxk_cuda_kernels.spgemm_forward_heads(indptr, indices, g, vals, sel,
-                                                            qf.shape[2]).mul_(ctx.scale)
+            fwd = mk.spgemm_forward_heads_x16 if x16 else mk.spgemm_forward_heads
+            grad_q = fwd(indptr, indices, g, vals, sel, qf.shape[2]).mul_(ctx.scale)
             grad_q = grad_q.to(ctx.q_dtype)
         if ctx.needs_input_grad[3]:
-            grad_tv = maxk_cuda_kernels.sspmm_backward_heads(indptr, indices, g, qf,
-                                                             sel).mul_(ctx.scale)
+            bwd = mk.sspmm_backward_heads_x16 if x16 else mk.sspmm_backward_heads
+            grad_tv = bwd(indptr, indices, g, qf, sel).mul_(ctx.scale)
         return None, None, grad_q, grad_tv, None, None
 
 
